@@ -12,7 +12,11 @@ data-path collective); one RCCL all-reduce of {bit errors, bits, samples,
 frames} and a MAX of the elapsed time at the end.
 
 Run: python bench.py [--gpus N --steps K --warmup W]; N>1 via
-torch.distributed.run (one process per GPU, RCCL over xGMI).
+torch.distributed.run (one process per GPU, RCCL over xGMI). A plain run sets
+up, warms up, times the K steps and prints the result line. --full adds
+everything else the line can hold: the config-4 stream records, the config-3
+record and the CPU baselines. --dump-outputs DIR writes what the last timed
+step computed (a fixed sample of its frames) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -30,6 +34,7 @@ from ofdm_synth import payload_bytes  # noqa: E402  (counter-based job payload)
 
 METRIC = "IQ-samples/sec (tx IFFT+CP and rx FFT+equalise), 2048-subcarrier frames, 1/2/4/8 GPU"
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md chip table: 8.0 TB/s spec
+CLOCK_RAMP_S = 0.06  # sustained load before a headline that no sub-record precedes (the clocks ramp over ~30 ms)
 CONFIG_B = dict(fft_size=2048, num_data_subc=1024, num_pilot_subc=32, cp_size=512, num_symb=8,
                 num_pr_symb=1, pr_sin_len=128, pr_seed=42, pr_level=500, t2sin_size=256, t2_sin_f1=17,
                 t2_sin_f2=51, t2_sin_level=800, smooth=5, mod_type=2, pilot_ampl=2500, mult=200,
@@ -485,6 +490,48 @@ def stream_ingest_leg(args, dev, M):
             "frac_of_pcie_ceiling": (layout.n / el) / (layout.n / h2d_s)}
 
 
+DUMP_BUDGET_BYTES = 56 << 20  # --dump-outputs writes at most this much over all ranks (below 64 MB)
+
+
+def dump_frames(nf: int, bytes_per_frame: int, budget: int) -> np.ndarray:
+    """The local frames --dump-outputs writes: the first, the last and a
+    seeded sample of the others, ascending, as many as fit the budget. A
+    function of its arguments alone, so two runs with the same arguments
+    write the same frames."""
+    n = int(min(nf, max(2, budget // bytes_per_frame)))
+    if n >= nf:
+        return np.arange(nf, dtype=np.int64)
+    mid = 1 + np.random.default_rng(20480).choice(nf - 2, n - 2, replace=False)
+    return np.sort(np.concatenate([[0, nf - 1], mid])).astype(np.int64)
+
+
+def dump_outputs(path: str, world: int, rank: int, f0: int, nf: int, msg: int, npts: int, bpf: int, iq, cons, out,
+                 errs):
+    """--dump-outputs: the arrays a caller of the timed step holds after the
+    last timed step, over dump_frames' sample of this rank's frames, as float64
+    / float32 .npy files (complex arrays as (..., 2) re/im pairs): tx's noisy
+    IQ, rx's constellation and bytes per sampled frame, and the bit-error
+    counter the caller passed (it counts over all the timed steps). Rank 0
+    writes <name>.npy, rank r > 0 <name>_rank<r>.npy."""
+    import torch
+    fr = dump_frames(nf, 16 * msg + 16 * npts + 4 * bpf, DUMP_BUDGET_BYTES // world)
+    sel = torch.from_numpy(fr).to(iq.device)
+
+    def pairs(z, per):  # complex128 (nf * per,) -> float64 (len(fr), per, 2)
+        return torch.view_as_real(z.view(nf, per)[sel]).cpu().numpy()
+    arrays = {"frames": (f0 + fr).astype(np.float64),  # global indices of the sampled frames
+              "iq": pairs(iq, msg),
+              "constell": pairs(cons, npts),
+              "bytes": out.view(nf, bpf)[sel].cpu().numpy().astype(np.float32),
+              "bit_errors": errs.cpu().numpy().astype(np.float64)}
+    os.makedirs(path, exist_ok=True)
+    suffix = f"_rank{rank}" if rank else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), a)
+    return {"dir": path, "frames": len(fr), "arrays": sorted(arrays),
+            "bytes": int(sum(a.nbytes for a in arrays.values()))}
+
+
 CONFIG_C = dict(CONFIG_B, fft_size=4096, num_data_subc=2048, num_pilot_subc=64, cp_size=1024, mod_type=4)
 
 
@@ -579,6 +626,12 @@ def main():
                          "a GPU (rehearsal of the multi-rank path on a 1-GPU box)")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=10, help="untimed steps (the GPU clocks ramp over the first ~10 launches)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the config-4 stream records, the config-3 record and the CPU "
+                         "baselines (each with its --no-... switch); off: the headline alone")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last one computed (noisy IQ, constellation, bytes of "
+                         "a fixed sample of the frames; the bit-error counter) as DIR/<name>.npy")
     ap.add_argument("--frames", type=int, default=8192, help="frames per GPU (8 symbols each); weak scaling")
     ap.add_argument("--total-frames", type=int, default=0,
                     help="strong scaling: shard this many frames over the GPUs (config 5: 30517 = 10 GB)")
@@ -631,7 +684,8 @@ def main():
         print(f"bench.py: WORLD_SIZE={world} (launcher) overrides --gpus {args.gpus}", file=sys.stderr)
     dist, dev = ofdm_dist.init(args.backend, local)
 
-    # Order: the headline's host-side setup (payload, buffers) first, then
+    # A plain run measures the headline alone. Order with --full: the
+    # headline's host-side setup (payload, buffers) first, then
     # the sub-records' GPU work (config-4 streams, config 3), then the
     # headline, then every CPU baseline. The headline is timed as the contract
     # says (W untimed warmup steps, then K timed steps) right after the
@@ -639,7 +693,9 @@ def main():
     # load (step time 1.31 ms over the first 10 steps, 1.18 ms from step 30:
     # profiles/r05_ramp.txt), and a host-side gap before the headline (the
     # payload's 0.8 s) would let them fall back. CPU baselines last: the GPU
-    # would idle meanwhile.
+    # would idle meanwhile. Where no sub-record ran, the warm-up begins with
+    # CLOCK_RAMP_S of the step itself, untimed, in place of that sustained
+    # work, so that W and K mean the same with and without --full.
     p = dict(CONFIG_B)
     modem = M.Modem(p, dev.index)
     geo = modem.geo
@@ -681,7 +737,7 @@ def main():
             sub[name] = {"error": repr(e)}
             print(f"bench.py: sub-record {name} failed: {e!r}", file=sys.stderr)
         torch.cuda.empty_cache()
-    if not args.no_stream:
+    if args.full and not args.no_stream:
         record("stream", lambda: stream_leg(args, dist, dev, world, rank, M, i16=False, deferred=deferred))
         record("stream_int16", lambda: stream_leg(args, dist, dev, world, rank, M, i16=True, deferred=deferred))
         if args.stream_b_frames > 0:  # the wide-geometry fused decode (config B frames) against the staged kernels
@@ -690,7 +746,7 @@ def main():
                                                   pipeline=False, staged_ab=True, deferred=deferred))
         if not args.no_ingest and world == 1:  # host ingest: one GPU's PCIe link
             record("stream_ingest", lambda: stream_ingest_leg(args, dev, M))
-    if not args.no_config3:
+    if args.full and not args.no_config3:
         record("config3", lambda: config3_leg(args, dist, dev, world, rank, M))
 
     def step(i, events=None):
@@ -703,6 +759,12 @@ def main():
         if events:
             events[2].record(stream)
 
+    if not sub:  # the clock ramp that the sub-records' kernels give the headline under --full
+        t_ramp = time.perf_counter()
+        while time.perf_counter() - t_ramp < CLOCK_RAMP_S:
+            for i in range(8):
+                step(i)
+            torch.cuda.synchronize(dev)
     for i in range(W):
         step(i)
     torch.cuda.synchronize(dev)
@@ -795,6 +857,10 @@ def main():
         os.makedirs(args.check_out, exist_ok=True)
         np.savez(os.path.join(args.check_out, f"rank{rank}.npz"), **dump)
         result["check"] = {"frames": want, "noise_std": noise_std, "seed": 1, "message_len": msg}
+    if args.dump_outputs:
+        torch.cuda.synchronize(dev)
+        result["dump_outputs"] = dump_outputs(args.dump_outputs, world, rank, f0, nf, msg, npts, bpf, iq, cons, out,
+                                              errs)
     modem.close()
     del iq, cons, out, data
 
@@ -806,7 +872,7 @@ def main():
             result["cpu_baseline"]["host_cpus"] = cpus
         except Exception as e:  # reported, not fatal: the GPU number stands alone
             result["cpu_baseline"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         deferred.insert(0, headline_cpu)
     result.update(sub)
     for fn in deferred:  # every CPU baseline, after the GPU measurements

@@ -48,7 +48,7 @@ def test_bench_strong_scaling_shards_total_frames():
 def test_bench_config3_record():
     # SURVEY §8d config 3 in the driver's bench line: the config-C loopback
     # step and the AWGN BER sweep (0..30 dB, >= 1e7 bits per point)
-    r = _bench("--steps", "2", "--warmup", "1", "--frames", "64", "--no-cpu-baseline", "--no-stream",
+    r = _bench("--full", "--steps", "2", "--warmup", "1", "--frames", "64", "--no-cpu-baseline", "--no-stream",
                "--config3-frames", "160")
     c3 = r["config3"]
     assert c3["n_gpus"] == 1 and c3["value"] > 0 and 0 < c3["roofline"]["frac"] < 1
@@ -66,7 +66,7 @@ def test_bench_stream_records():
     # config-B frames' wide fused decode beside the staged kernels, and the
     # host-ingest record (outputs equal to the device-resident call); the
     # two-context figure is off by default (one context per GPU)
-    r = _bench("--steps", "1", "--warmup", "1", "--frames", "64", "--no-cpu-baseline", "--no-config3",
+    r = _bench("--full", "--steps", "1", "--warmup", "1", "--frames", "64", "--no-cpu-baseline", "--no-config3",
                "--stream-frames", "512", "--stream-reps", "2", "--stream-warmup", "1", "--stream-b-frames", "96",
                "--ingest-chunk", "300000", "--ingest-reps", "1")
     for key in ("stream", "stream_int16"):
@@ -88,9 +88,35 @@ def test_bench_stream_records():
 def test_bench_two_context_stream_figure_on_request():
     # --stream-pipeline 2: two contexts on two HIP streams taking calls in
     # turn (an experiment, off by default); outputs equal the serial calls'
-    r = _bench("--steps", "1", "--warmup", "1", "--frames", "64", "--no-cpu-baseline", "--no-config3",
+    r = _bench("--full", "--steps", "1", "--warmup", "1", "--frames", "64", "--no-cpu-baseline", "--no-config3",
                "--stream-frames", "512", "--stream-reps", "2", "--stream-warmup", "1", "--stream-b-frames", "0",
                "--no-ingest", "--stream-pipeline", "2")
     for key in ("stream", "stream_int16"):
         pp = r[key]["pipelined"]
         assert pp["contexts"] == 2 and pp["calls"] == 4 and pp["outputs_match_serial"] is True and pp["value"] > 0
+
+
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    # without --full: no sub-record, no CPU baseline; --dump-outputs writes the
+    # last timed step's arrays (all 64 frames fit the budget) as float .npy
+    # files, which the oracle reproduces from the dumped noisy IQ
+    import numpy as np
+    import oracle as O
+    d = str(tmp_path / "dump")
+    r = _bench("--steps", "2", "--warmup", "1", "--frames", "64", "--dump-outputs", d)
+    assert r["steps"] == 2 and r["ms_per_step"] > 0 and r["cpu_baseline"] is None
+    assert not {"stream", "stream_int16", "stream_B", "stream_ingest", "config3"} & set(r)
+    got = {n: np.load(os.path.join(d, n + ".npy")) for n in r["dump_outputs"]["arrays"]}
+    assert sorted(got) == ["bit_errors", "bytes", "constell", "frames", "iq"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(a.nbytes for a in got.values()) == r["dump_outputs"]["bytes"] <= 64 << 20
+    g = O.geometry(O.CONFIG_B)
+    assert got["frames"].tolist() == list(range(64))
+    assert got["iq"].shape == (64, g["message_len"], 2) and got["constell"].shape == (64, g["npts"], 2)
+    assert got["bytes"].shape == (64, g["bytes_per_frame"])
+    assert got["bit_errors"].tolist() == [r["bit_errors"]]
+    iq = got["iq"][..., 0] + 1j * got["iq"][..., 1]
+    cons, out, _ = O.rx_batch(O.CONFIG_B, iq.reshape(-1), 64, g["message_len"])
+    assert np.array_equal(got["bytes"].astype(np.uint8).reshape(-1), out)
+    c = got["constell"][..., 0] + 1j * got["constell"][..., 1]
+    assert np.abs(c.reshape(-1) - cons).max() / np.abs(cons).max() < 1e-9

@@ -142,3 +142,20 @@ def test_bench_gpus_flag_launches_ranks(monkeypatch):
         bench.main()
     assert e.value.code == 0
     assert calls == [(4, os.path.join(root, "bench.py"), ["--gpus", "4", "--steps", "3"])]
+
+
+def test_bench_dump_frames_sample_is_fixed_and_within_budget():
+    """--dump-outputs' frame sample at the headline size: the same frames on
+    every call, ascending without repeats, the first and last frame among
+    them, and as many as fit the budget (every frame when all fit)."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    per = 16 * 20480 + 16 * 8192 + 4 * 2048  # config B: noisy IQ + constellation + bytes (as float32) of a frame
+    fr = bench.dump_frames(8192, per, bench.DUMP_BUDGET_BYTES)
+    assert np.array_equal(fr, bench.dump_frames(8192, per, bench.DUMP_BUDGET_BYTES))
+    assert fr[0] == 0 and fr[-1] == 8191 and np.all(np.diff(fr) > 0)
+    assert len(fr) == bench.DUMP_BUDGET_BYTES // per and len(fr) * per + 1024 <= 64 << 20
+    assert np.array_equal(bench.dump_frames(64, per, bench.DUMP_BUDGET_BYTES), np.arange(64))
+    assert np.array_equal(bench.dump_frames(1, per, bench.DUMP_BUDGET_BYTES), [0])
+    assert np.array_equal(bench.dump_frames(9, per, 2 * per), [0, 8])

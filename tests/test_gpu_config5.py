@@ -75,7 +75,7 @@ def test_config5_10gb_rccl_one_rank_and_gloo_two_ranks(tmp_path):
     d1 = str(tmp_path / "nccl")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr=127.0.0.1", f"--master-port={free_port()}", os.path.join(ROOT, "bench.py"), *common,
-           "--backend", "nccl", "--check-out", d1, "--stream-frames", "2048", "--stream-reps", "1",
+           "--full", "--backend", "nccl", "--check-out", d1, "--stream-frames", "2048", "--stream-reps", "1",
            "--stream-warmup", "1", "--stream-pipeline", "1"]
     r = subprocess.run(cmd, env=_env(), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -4,7 +4,7 @@
 #   gpurun_out/prof_fetch   --pmc FETCH_SIZE   (separate pass, as MI355X_MICROARCH.md prescribes)
 #   gpurun_out/prof_write   --pmc WRITE_SIZE
 #   gpurun_out/pmc_rx.json  HBM bytes per rx launch (tools/pmc_traffic.py)
-#   gpurun_out/bench.json   the bench line
+#   standard output         the bench line (every record: bench.py --full)
 export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 mkdir -p $R/gpurun_out
@@ -15,4 +15,4 @@ timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $R/gpurun_ou
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $R/gpurun_out/prof_write -o run -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-stream --no-config3 > gpurun_out/prof_write.log 2>&1 && \
 python3 tools/pmc_traffic.py gpurun_out/prof_fetch/run_counter_collection.csv gpurun_out/prof_write/run_counter_collection.csv "rx_kernel<11" $W gpurun_out/pmc_rx.json 3238002688 > /dev/null && \
 python3 tools/pmc_traffic.py gpurun_out/prof_fetch/run_counter_collection.csv gpurun_out/prof_write/run_counter_collection.csv "tx_kernel<11" $W gpurun_out/pmc_tx.json 2700083200 > /dev/null && \
-timeout -k 10 400 python bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err
+timeout -k 10 600 python bench.py --full

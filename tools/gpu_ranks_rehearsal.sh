@@ -5,8 +5,8 @@
 export TMPDIR=/tmp
 mkdir -p gpurun_out
 for n in ${RANKS:-2 4}; do
-  extra="--no-config3 --stream-b-frames 0"
-  [ -n "$SMALL" ] && extra="--frames 1024 --stream-frames 2048 --stream-b-frames 512 --config3-frames 512 --stream-warmup 5 --config3-warmup 5"
+  extra="--full --no-config3 --stream-b-frames 0"
+  [ -n "$SMALL" ] && extra="--full --frames 1024 --stream-frames 2048 --stream-b-frames 512 --config3-frames 512 --stream-warmup 5 --config3-warmup 5"
   timeout -k 10 900 python bench.py --gpus $n --backend gloo --no-cpu-baseline $extra > gpurun_out/ranks$n.json 2> gpurun_out/ranks$n.err || { tail -20 gpurun_out/ranks$n.err; exit 1; }
   python3 -c "
 import json; d=json.load(open('gpurun_out/ranks$n.json'))

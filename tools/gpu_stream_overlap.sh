@@ -5,7 +5,8 @@ export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 mkdir -p $R/gpurun_out
 D=$R/gpurun_out/ov_prof; rm -rf $D
-timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv -d $D -o run -- python3 bench.py --no-cpu-baseline --no-config3 --stream-b-frames 0 --no-ingest --stream-pipeline 2 --steps 5 --warmup 5 > gpurun_out/ov_bench.json 2> gpurun_out/ov_bench.err || { tail gpurun_out/ov_bench.err; exit 1; }
+O=${D%/*}  # the output folder: the bench line and its stderr go beside the trace
+timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv -d $D -o run -- python3 bench.py --full --no-cpu-baseline --no-config3 --stream-b-frames 0 --no-ingest --stream-pipeline 2 --steps 5 --warmup 5 > $O/ov_bench.json 2> $O/ov_bench.err || { tail $O/ov_bench.err; exit 1; }
 python3 -c "
 import json; d=json.load(open('gpurun_out/ov_bench.json'))
 for k in ('stream','stream_int16'):

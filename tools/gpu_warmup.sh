@@ -1,7 +1,8 @@
 #!/bin/bash
 # the headline's dependence on warmup (driver: --steps 20 --warmup 5), same box:
-# "first" = the headline alone (as the first GPU work of the process, cold
-# clocks); "last" = bench.py's order (the sub-records' GPU work first)
+# "first" = the headline alone (the first GPU work of the process, behind
+# bench.py's own 60 ms clock ramp); "last" = bench.py's --full order (the
+# sub-records' GPU work first)
 export TMPDIR=/tmp
 mkdir -p gpurun_out
 OUT=gpurun_out/r05_warmup.txt; : > $OUT
@@ -9,7 +10,7 @@ for r in 1 2; do
   for w in 5 10 50; do
     for order in first last; do
       extra="--no-stream --no-config3"
-      [ $order = last ] && extra=""
+      [ $order = last ] && extra="--full"
       timeout -k 10 400 python bench.py --steps 20 --warmup $w --no-cpu-baseline $extra > gpurun_out/wu.json 2> gpurun_out/wu.err || { tail gpurun_out/wu.err; exit 1; }
       python3 -c "
 import json; d=json.load(open('gpurun_out/wu.json'))
