@@ -954,7 +954,7 @@ int ofdm_tx_frames(ofdm_ctx* c, const uint8_t* bytes, size_t nframes, double* fr
 static int rx_demod_impl(ofdm_ctx* c, const double* iq, const int16_t* iq16, size_t nframes, size_t frame_stride,
                          const double* chan, size_t chan_stride, double* constell_out, uint8_t* bytes_out,
                          const uint8_t* ref_bytes, unsigned long long* bit_errors, void* stream,
-                         double* read_out = nullptr)
+                         double* read_out = nullptr, const ofdm::SoftArgs* soft = nullptr)
 {
     if (!c || (!iq && !iq16)) return fail(OFDM_ERR_INVALID, "null argument");
     if (iq16 && ((uintptr_t)iq16 & 3)) return fail(OFDM_ERR_INVALID, "iq16 must be 4-byte aligned");
@@ -1006,11 +1006,24 @@ static int rx_demod_impl(ofdm_ctx* c, const double* iq, const int16_t* iq16, siz
             a.ystage = c->d_scratch;
         }
     }
-    hipError_t e = ofdm::launch_rx(c->logn, a, (hipStream_t)stream, nullptr);
+    hipError_t e = soft ? ofdm::launch_rx_soft(c->logn, a, *soft, (hipStream_t)stream)
+                        : ofdm::launch_rx(c->logn, a, (hipStream_t)stream, nullptr);
     if (e != hipSuccess) {
         rx_queue_reset(c, a.queue, (hipStream_t)stream);
         return hip_fail(e, "rx_kernel launch");
     }
+    return OFDM_OK;
+}
+
+// Argument checks shared by the two soft entry points.
+static int soft_args_check(const ofdm_ctx* c, double scale, int fmt, const void* llr_out)
+{
+    if (!c || !llr_out) return fail(OFDM_ERR_INVALID, "null argument");
+    if (fmt != OFDM_LLR_F32 && fmt != OFDM_LLR_I8) return fail(OFDM_ERR_INVALID, "fmt is not OFDM_LLR_F32 / OFDM_LLR_I8");
+    if (!std::isfinite(scale) || !(scale > 0.0)) return fail(OFDM_ERR_INVALID, "scale must be finite and > 0");
+    if (fmt == OFDM_LLR_F32 && ((uintptr_t)llr_out & 3)) return fail(OFDM_ERR_INVALID, "llr_out must be 4-byte aligned");
+    if (c->k != 1 && c->k != 2 && c->k != 4 && c->k != 6 && c->k != 8)
+        return fail(OFDM_ERR_UNSUPPORTED, "soft demapping covers modType 1, 2, 4, 6, 8 (not %d)", (int)c->k);
     return OFDM_OK;
 }
 
@@ -1049,6 +1062,31 @@ int ofdm_demap(ofdm_ctx* c, double* points, size_t n, uint8_t* bytes_out, void* 
     hipError_t e = ofdm::launch_demap(reinterpret_cast<double2*>(points), (long)n, c->k, bytes_out, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "demap launch");
     return OFDM_OK;
+}
+
+int ofdm_soft_demap(ofdm_ctx* c, const double* points, size_t n, double scale, int fmt, void* llr_out, void* stream)
+{
+    if (!c || !points) return fail(OFDM_ERR_INVALID, "null argument");
+    if (int rc = soft_args_check(c, scale, fmt, llr_out)) return rc;
+    if (!aligned16(points)) return fail(OFDM_ERR_INVALID, "points must be 16-byte aligned");
+    hipError_t e = ofdm::launch_soft_demap(reinterpret_cast<const double2*>(points), (long)n, c->k, scale, fmt, llr_out,
+                                           (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "soft demap launch");
+    return OFDM_OK;
+}
+
+int ofdm_rx_demod_soft(ofdm_ctx* c, const double* iq, const int16_t* iq16, size_t nframes, size_t frame_stride,
+                       const double* chan, size_t chan_stride, double scale, const double* frame_scale, int fmt,
+                       void* llr_out, double* constell_out, uint8_t* bytes_out, const uint8_t* ref_bytes,
+                       unsigned long long* bit_errors, void* stream)
+{
+    if (!c) return fail(OFDM_ERR_INVALID, "null argument");
+    if ((iq == nullptr) == (iq16 == nullptr)) return fail(OFDM_ERR_INVALID, "exactly one of iq, iq16");
+    if (int rc = soft_args_check(c, scale, fmt, llr_out)) return rc;
+    if (frame_scale && ((uintptr_t)frame_scale & 7)) return fail(OFDM_ERR_INVALID, "frame_scale must be 8-byte aligned");
+    ofdm::SoftArgs sa{llr_out, frame_scale, scale, fmt};
+    return rx_demod_impl(c, iq, iq16, nframes, frame_stride, chan, chan_stride, constell_out, bytes_out, ref_bytes,
+                         bit_errors, stream, nullptr, &sa);
 }
 
 int ofdm_map(ofdm_ctx* c, const uint8_t* bytes, size_t nbytes, double* points_out, void* stream)

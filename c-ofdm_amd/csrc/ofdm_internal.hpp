@@ -78,7 +78,18 @@ struct RxArgs {
     double pilot_ampl;
 };
 
+// The soft rx's own arguments (rx_soft_kernel's second parameter: RxArgs and
+// with it every rx_kernel instantiation stay as they are).
+struct SoftArgs {
+    void* llr;                  // nframes*S*D*k LLRs: float (OFDM_LLR_F32) or int8 (OFDM_LLR_I8)
+    const double* frame_scale;  // nullable, device: frame f uses scale * frame_scale[f]
+    double scale;
+    int fmt;
+};
+
 // Launchers (ofdm_kernels.hip). Return hipSuccess or the launch error.
+hipError_t launch_rx_soft(int logn, const RxArgs& a, const SoftArgs& sa, hipStream_t stream);
+hipError_t launch_soft_demap(const double2* pts, long n, int k, double scale, int fmt, void* out, hipStream_t stream);
 hipError_t launch_tx(int logn, const TxArgs& a, hipStream_t stream);
 hipError_t launch_rx(int logn, const RxArgs& a, hipStream_t stream, bool* staged_needed);
 hipError_t launch_copy(void* dst, const void* src, size_t n, hipStream_t stream);  // kernel copy (device / mapped pinned)

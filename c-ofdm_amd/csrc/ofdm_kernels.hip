@@ -14,6 +14,9 @@
 //                 — one workgroup per frame; the frame's data carriers stay in
 //                 VGPRs until the frame-global pilot normalisation is known.
 //   demap/map   : Modulation::demod / ::mod on flat point arrays.
+//   soft        : max-log LLRs (float32 / int8) for a channel decoder behind the
+//                 core: soft_demap_kernel on flat points, rx_soft_kernel = rx_kernel
+//                 that also writes them (body shared as text: ofdm_rx_body.inc).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdint>
@@ -538,355 +541,29 @@ __device__ __forceinline__ double2 stage_get(const void* stage, int e)
     }
 }
 
+
+// The kernel's body is ofdm_rx_body.inc, included as text by rx_kernel and by
+// rx_soft_kernel (SOFT: the launch also writes the max-log LLRs of every
+// equalised point, ofdm_dev.hpp soft_emit). Everything the soft path adds
+// sits under `if constexpr (SOFT)`, which rx_kernel discards before code
+// generation: its instantiations are register-tight (a wrapper around a
+// shared inlined function already moved their allocation), and stay the code
+// they were.
 template <int LOGN, bool STAGED, bool I16, bool SYNC>
 __global__ void __launch_bounds__((1 << LOGN) / 8, 2) rx_kernel(RxArgs a)
 {
-    using FS = FftShape<LOGN>;
-    constexpr int N = FS::N, T = FS::T;
-    constexpr int SW = STAGED ? 1 : RX_SMAX;  // register window (symbols)
-    extern __shared__ double2 smem[];
-    const int S0 = a.S, P0 = a.P;
-    double2* bufA = smem;                   // FFT ping-pong images
-    double2* bufB = bufA + N;
-    double2* lds_tw = bufB + FS::PADN;      // TwLds::SIZE
-    double2* pil = lds_tw + TwLds<LOGN>::SIZE;  // S*P raw pilots
-    double2* gain = pil + S0 * P0;          // S*P equaliser gains
-    double* red = reinterpret_cast<double*>(gain + S0 * P0);
-    uint8_t* dec = reinterpret_cast<uint8_t*>(bufA);  // aliases the FFT images after the transforms
+    constexpr bool SOFT = false;
+    const SoftArgs sa{};  // never read
+#include "ofdm_rx_body.inc"
+}
 
-    const int t0 = threadIdx.x;
-    const int L = N + a.cp;
-    const long fstep = gridDim.x;
-    // frames to process: a.nframes, or fewer when the count is device-side
-    // (speculative stream decode); uniform early exit before any prefetch
-    // stream mode: a first frame whose preamble starts before the stream's
-    // first sample is the host's (gather path, zeros before sample 0): the
-    // frames taken here are fbase, fbase + 1, ...
-    const long fbase = (SYNC && a.nframes > 0 && (!a.count || *a.count > 0) && a.starts[0] < 0) ? 1 : 0;
-    const long nfr = (a.count ? min(*a.count, a.nframes) : a.nframes) - fbase;
-    // Dynamic frames (a.queue): a workgroup's first frame is its blockIdx,
-    // later ones come from a counter, so workgroups that run faster (CU and
-    // memory-channel placement make them differ by ~15%) take more frames and
-    // the kernel ends with the mean workgroup, not the slowest. The last
-    // workgroup to leave zeroes the counters for the next launch.
-    auto leave = [&]() {
-        if (a.queue && threadIdx.x == 0) {
-            __threadfence();
-            if (atomicAdd(a.queue + 1, 1) == (int)gridDim.x - 1) {
-                a.queue[0] = 0;
-                a.queue[1] = 0;
-            }
-        }
-    };
-    if ((long)blockIdx.x >= nfr) {
-        leave();
-        return;
-    }
-    int* qslot = reinterpret_cast<int*>(red + 16);  // the next frame from the queue (red[0..7]: reductions)
-
-    // table loads first, then symbol 0 of the first frame: every prologue wait
-    // below is a counted vmcnt that leaves the symbol prefetch in flight
-    constexpr bool kTwSplit = T >= TwLds<LOGN>::SIZE;
-    TwPiece<LOGN> twp{};
-    if constexpr (kTwSplit)
-        twp = tw_fetch<LOGN>(a.tab.tw, t0);
-    else
-        load_twiddles<LOGN>(a.tab.tw, lds_tw, t0, T);
-    // data carrier d = t0 + T*i: swizzled LDS slot of its FFT bin (low 16 bits)
-    // | pilot slot (high 16); host tables are zero-padded, so no guards here
-    int pk[RX_DPT];
-#pragma unroll
-    for (int i = 0; i < RX_DPT; ++i) pk[i] = a.tab.rx_pack[t0 + T * i];
-    const int pbin = a.tab.pilot_swz[t0];
-    long fl = blockIdx.x;  // this workgroup's frame
-    auto frame_of = [&](long l) { return l + fbase; };
-    SymbolRegs<LOGN, I16> pf;
-    // sample offset of frame g's first message body (CP strip, Frame.hpp:278-279)
-    auto body0 = [&](long g) { return SYNC ? a.starts[g] + a.start_off : g * a.frame_stride + a.cp; };
-    dma_symbol<LOGN, I16>(a, body0(frame_of(fl)), bufB, t0);  // grid <= nframes
-    if constexpr (kTwSplit) tw_store<LOGN>(twp, lds_tw);
-    lds_barrier();  // twiddle table visible: fft_pp reads a pass's twiddles before its barrier
-
-    unsigned long long errs = 0;
-
-    // Persistent over frames (grid <= 2 workgroups per CU): the next frame's
-    // symbol 0 is fetched (LDS-DMA into bufB) while this frame's epilogue
-    // runs, so HBM reads do not stop between frames, and the tables are
-    // loaded once per workgroup.
-#pragma unroll 1
-    for (long fnext; fl < nfr; fl = fnext) {
-        const long f = frame_of(fl);
-        // Opaque per-frame copies of the thread index, the carrier tables and
-        // the geometry: everything derived from them is recomputed per frame
-        // instead of being hoisted out of the frame loop and held live beside
-        // the register window (which spills).
-        int t;
-        asm volatile("v_mov_b32 %0, %1" : "=v"(t) : "v"(t0));
-#pragma unroll
-        for (int i = 0; i < RX_DPT; ++i) asm volatile("" : "+v"(pk[i]));
-        int S = a.S, D = a.D, P = a.P;
-        asm volatile("" : "+s"(S), "+s"(D), "+s"(P));
-        const long x0 = body0(f);
-        const int m = 1 << (a.k / 2);
-        const double s1 = a.k == 1 ? 0.0 : 1.0 / (2.0 / (m - 1));
-        const bool whole_frame_dec = (long)S * D <= (long)FS::PADN * 16;
-        const long bpf = a.bytes_per_frame;
-        // word-wise packing: k in {1,2,4,8}, whole words, 4-byte aligned outputs
-        const bool by_word = (a.k == 1 || a.k == 2 || a.k == 4 || a.k == 8) && (bpf & 3) == 0 &&
-                             ((uintptr_t)a.bytes & 3) == 0 && ((uintptr_t)a.ref & 3) == 0;
-        double2 y[SW][RX_DPT];
-        // symbol 0 is read from bufB, so pass 0 writes bufA (free: the
-        // previous epilogue ended with a barrier)
-        double2* first = bufA;
-        double2* second = bufB;
-#pragma unroll 1
-        for (int s = 0; s < S; ++s) {
-            double2 v[8];
-            if (s == 0) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's DMA of symbol 0 landed
-#pragma unroll
-                for (int i = 0; i < 8; ++i) v[i] = stage_get<LOGN, I16>(bufB, t + T * i);
-            } else {
-#pragma unroll
-                for (int i = 0; i < 8; ++i) v[i] = pf.get(i);
-            }
-            // SYNC: the phase ramp is applied before the next symbol's
-            // prefetch is issued, so its sincos temporaries are not live
-            // beside the 8 prefetch registers (which spilled at N = 512)
-            if (!SYNC && s + 1 < S) pf.load(a, x0 + (long)(s + 1) * L, t);
-            if constexpr (SYNC) {
-                // sample m = t + T*i of the body: *= e^{i(A + B m)}, by a
-                // running product from e^{i(A + B t)} in steps of e^{i B T};
-                // e^{i(A + B t)} from the table (uniform loads), the bits of t
-                // selecting its powers (x (1, 0) is exact)
-                // (the bit tests on a per-symbol opaque copy of t: hoisted
-                // out of the loop, their lane masks filled the SGPRs and spilled)
-                const double2* rt = a.corr + (f * S + s) * CORR_PER_SYM;
-                int tr;
-                asm volatile("v_mov_b32 %0, %1" : "=v"(tr) : "v"(t));
-                double2 c = rt[0];
-#pragma unroll
-                for (int j = 0; j < LOGN - 3; ++j) c = cmul_exact(c, (tr >> j) & 1 ? rt[1 + j] : make_double2(1.0, 0.0));
-                const double2 w = rt[CORR_PER_SYM - 1];
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    v[i] = cmul(v[i], c);
-                    if (i < 7) c = cmul(c, w);
-                }
-                asm volatile("" ::: "memory");  // keep the prefetch below the ramp
-                if (s + 1 < S) pf.load(a, x0 + (long)(s + 1) * L, t);
-            }
-            // opaque copy of t: the per-pass LDS addresses are recomputed each
-            // symbol instead of being hoisted out of the loop and held live
-            // beside the register window
-            int tl;
-            asm volatile("v_mov_b32 %0, %1" : "=v"(tl) : "v"(t));
-            double2* res = fft_pp<LOGN, -1>(v, tl, lds_tw, first, second);
-            first = res == bufA ? bufB : bufA;
-            second = res;
-            if (t < P) pil[s * P + t] = res[pbin];
-            if constexpr (STAGED) {
-#pragma unroll
-                for (int i = 0; i < RX_DPT; ++i) {
-                    const int d = t + T * i;
-                    if (d < D) a.ystage[(f * S + s) * D + d] = res[pk[i] & 0xffff];
-                }
-            } else {
-                switch (s) {
-#define OFDM_RX_PUT(W)                                                                    \
-    case W:                                                                               \
-        if constexpr (W < SW) {                                                           \
-            _Pragma("unroll") for (int i = 0; i < RX_DPT; ++i) y[W][i] = res[pk[i] & 0xffff]; \
-        }                                                                                 \
-        break;
-                    OFDM_RX_PUT(0) OFDM_RX_PUT(1) OFDM_RX_PUT(2) OFDM_RX_PUT(3)
-                    OFDM_RX_PUT(4) OFDM_RX_PUT(5) OFDM_RX_PUT(6) OFDM_RX_PUT(7)
-#undef OFDM_RX_PUT
-                    default: break;
-                }
-            }
-        }
-        lds_barrier();  // pilots of the last symbol visible; every thread is done reading bufB
-        // The channel carriers go to LDS (bufA past the decisions) by DMA
-        // issued ahead of the next frame's symbol 0: read per point from HBM
-        // behind that DMA (in-order returns), they cost the stream rx ~18%.
-        const double2* chan = a.chan ? a.chan + f * a.chan_stride : nullptr;
-        const int dec_b = (S * D + 15) & ~15;
-        double2* chl = reinterpret_cast<double2*>(reinterpret_cast<char*>(bufA) + dec_b);
-        const bool chan_lds = chan && dec_b + D * 16 <= N * 16;  // uniform
-        if (chan_lds) dma_chan<LOGN>(chan, D, chl, t);
-        // Static frame order (no queue; the stream decode): the next frame's
-        // symbol 0 streams into bufB (free since the pilot barrier) from here,
-        // behind the channel carriers, so it overlaps the gains as well.
-        // With the queue the next frame is asked for now, its answer awaited
-        // after the gains (the register holding it is live across the gains
-        // only), and its DMA issued after them.
-        const bool early = !a.queue;  // uniform
-        if (early) {
-            fnext = fl + fstep;
-            if (fnext < nfr) dma_symbol<LOGN, I16>(a, body0(frame_of(fnext)), bufB, t);
-        }
-        int qv = 0;
-        if (a.queue && t == 0) qv = atomicAdd(a.queue, 1);
-
-        // phys_pilot_ampl = sum |pilot| / (P*S*pilot_ampl)   (Frame.cpp:76-80)
-        double acc = 0.0;
-        for (int i = t; i < S * P; i += T) acc += hypot(pil[i].x, pil[i].y);
-        acc = block_sum_lds<T>(acc, red);
-        const double phys = acc / ((double)(P * S) * a.pilot_ampl);
-
-        // out = (F/phys) / ((F[s,p]/phys) / (F[0,p]/phys)) = F * gain[s][j]   (Frame.cpp:82-93)
-        for (int i = t; i < S * P; i += T) {
-            const int j = i % P;
-            const double2 c0 = make_double2(pil[j].x / phys, pil[j].y / phys);
-            const double2 cs = make_double2(pil[i].x / phys, pil[i].y / phys);
-            const double2 coef = cdiv_exact(cs, c0);
-            const double2 g = cdiv_exact(make_double2(1.0, 0.0), coef);
-            gain[i] = make_double2(g.x / phys, g.y / phys);
-        }
-        if (chan_lds) {  // the channel DMA landed (the 8 symbol-0 transfers issued after it may still fly)
-            if (early && fnext < nfr)
-                asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-            else
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        if (a.queue && t == 0) *qslot = qv;
-        lds_barrier();
-        if (!early) {
-            // symbol 0 of the next frame streams into bufB behind the emit and
-            // the packing
-            fnext = fstep + __builtin_amdgcn_readfirstlane(*qslot);  // uniform: an SGPR
-            if (fnext < nfr) dma_symbol<LOGN, I16>(a, body0(frame_of(fnext)), bufB, t);
-        }
-
-        // One symbol's RX_DPT points of the register window. Without a
-        // channel (the common case) the group's gain loads are issued first
-        // and the points then computed, stored and decided; the uniform
-        // branches are taken once per group, so the points' LDS latencies
-        // overlap. With a channel, one point at a time (register pressure).
-        auto emit_point = [&](int s, int i, double2 yv) {
-            // opaque: the per-point addresses are computed here, not hoisted
-            // out of the emit loop and held (32 of them) across it
-            int d = t + T * i, gi = s * P + (pk[i] >> 16);
-            asm volatile("" : "+v"(d), "+v"(gi));
-            double2 o = cmul_exact(yv, gain[gi]);
-            if (a.read_out) store_nt(a.read_out + (f * S + s) * D + d, o);
-            const double2 cv = chan_lds ? chl[d] : load_untracked(chan + d);
-            o = a.chan_recip ? cmul_exact(o, cv) : cdiv_exact(o, cv);
-            if (a.constell) store_nt(a.constell + (f * S + s) * D + d, o);
-            dec[whole_frame_dec ? s * D + d : d] = (uint8_t)decide(o, a.k, s1, m);
-        };
-        // Without a channel (the common case) a group is straight-line code:
-        // the output branch is taken once per group and the decision is
-        // branch-free, so the scheduler can overlap the points' LDS reads.
-        auto emit_plain = [&](int s, const double2 (&yw)[RX_DPT], auto with_store) {
-            double2* cbase = a.constell + (f * S + s) * D;
-#pragma unroll
-            for (int i = 0; i < RX_DPT; ++i) {
-                int d = t + T * i, gi = s * P + (pk[i] >> 16);
-                asm volatile("" : "+v"(d), "+v"(gi));  // opaque: not hoisted and held
-                if (d < D) {
-                    const double2 o = cmul_exact(yw[i], gain[gi]);
-                    if constexpr (decltype(with_store)::value) store_nt(cbase + d, o);
-                    dec[whole_frame_dec ? s * D + d : d] = (uint8_t)decide_select(o, a.k, s1, m);
-                }
-            }
-        };
-        auto emit_group = [&](int s, const double2 (&yw)[RX_DPT]) {
-            if (SYNC || chan) {  // the stream decode always has its channel
-#pragma unroll
-                for (int i = 0; i < RX_DPT; ++i)
-                    if (t + T * i < D) emit_point(s, i, yw[i]);
-            } else if (a.constell) {
-                emit_plain(s, yw, std::true_type{});
-            } else {
-                emit_plain(s, yw, std::false_type{});
-            }
-        };
-
-        auto pack = [&](long jb0, long jb1, long dbase) {
-            for (long jb = jb0 + t; jb < jb1; jb += T) {
-                int byte = 0;
-                if (a.k == 1 || a.k == 2 || a.k == 4 || a.k == 8) {
-                    const int per = 8 / a.k;
-                    const long p0 = (jb - jb0) * per + dbase;
-                    for (int r = 0; r < per; ++r) byte = (byte << a.k) | dec[p0 + r];
-                } else {
-                    for (int b = 0; b < 8; ++b) {
-                        const long bit = (jb - jb0) * 8 + b;
-                        const long g = bit / a.k + dbase;
-                        const int within = (int)(bit % a.k);
-                        byte = (byte << 1) | ((dec[g] >> (a.k - 1 - within)) & 1);
-                    }
-                }
-                if (a.bytes) a.bytes[f * bpf + jb] = (uint8_t)byte;
-                if (a.ref) errs += __popc((unsigned)(byte ^ a.ref[f * bpf + jb]));
-            }
-        };
-
-        auto pack_words = [&]() {
-            const int per_word = 32 / a.k;  // decisions per output word
-            for (long w = t; w < bpf / 4; w += T) {
-                const uint8_t* dw = dec + w * per_word;
-                uint32_t word;
-                switch (a.k) {
-                    case 1: word = pack_word<1>(dw); break;
-                    case 2: word = pack_word<2>(dw); break;
-                    case 4: word = pack_word<4>(dw); break;
-                    default: word = pack_word<8>(dw); break;
-                }
-                if (a.bytes) reinterpret_cast<uint32_t*>(a.bytes + f * bpf)[w] = word;
-                if (a.ref) errs += __popc(word ^ reinterpret_cast<const uint32_t*>(a.ref + f * bpf)[w]);
-            }
-        };
-
-        if constexpr (!STAGED) {
-            // one symbol per (non-unrolled) iteration: a case's register
-            // indices are compile-time, and the scheduler cannot interleave
-            // symbols (the next frame's symbol 0 is live in registers here)
-#pragma unroll 1
-            for (int w = 0; w < S; ++w) {
-                switch (w) {
-#define OFDM_RX_EMIT(W)                 \
-    case W:                             \
-        if constexpr (W < SW) {         \
-            emit_group(w, y[W]);        \
-        }                               \
-        break;
-                    OFDM_RX_EMIT(0) OFDM_RX_EMIT(1) OFDM_RX_EMIT(2) OFDM_RX_EMIT(3)
-                    OFDM_RX_EMIT(4) OFDM_RX_EMIT(5) OFDM_RX_EMIT(6) OFDM_RX_EMIT(7)
-#undef OFDM_RX_EMIT
-                    default: break;
-                }
-            }
-            lds_barrier();
-            if (by_word)
-                pack_words();
-            else
-                pack(0, bpf, 0);
-        } else {
-            const long bps = (long)D * a.k / 8;  // bytes per symbol (host checks D*k % 8 == 0)
-            for (int s = 0; s < S; ++s) {
-                double2 yst[RX_DPT];
-#pragma unroll
-                for (int i = 0; i < RX_DPT; ++i)
-                    yst[i] = t + T * i < D ? a.ystage[(f * S + s) * D + t + T * i] : make_double2(0.0, 0.0);
-                emit_group(s, yst);
-                lds_barrier();
-                if (!whole_frame_dec) {
-                    pack(s * bps, (s + 1) * bps, 0);
-                    lds_barrier();
-                }
-            }
-            if (whole_frame_dec) pack(0, bpf, 0);
-        }
-        lds_barrier();  // dec / pil / gain / red are rewritten by the next frame
-    }
-    if (a.bit_errors) {
-        errs = block_sum_u64<T>(errs, red);
-        if (t0 == 0 && errs) atomicAdd(a.bit_errors, errs);
-    }
-    leave();
+// rx_kernel that also writes the LLRs (ofdm_rx_demod_soft): every geometry of
+// the batched rx, f64 or int16 input, never the stream mode.
+template <int LOGN, bool STAGED, bool I16>
+__global__ void __launch_bounds__((1 << LOGN) / 8, 2) rx_soft_kernel(RxArgs a, SoftArgs sa)
+{
+    constexpr bool SOFT = true, SYNC = false;
+#include "ofdm_rx_body.inc"
 }
 
 // ------------------------------------------------------------------ rx for a few frames
@@ -1095,6 +772,51 @@ __global__ void demap_kernel(double2* pts, long n, int k, uint8_t* bytes, long n
     bytes[jb] = (uint8_t)byte;
 }
 
+// Max-log LLRs of n flat points (ofdm_soft_demap; definition: ofdm_dev.hpp).
+// Memory bound: 16 B in and k (int8) or 4k (f32) bytes out per point. A tile
+// of 256 x 4 points is loaded 16 B per lane, coalesced (point t + 256*i); each
+// lane writes its points' LLRs to the LDS image of the tile's output, which
+// then leaves as whole 16-B words per lane whatever k is (element by element
+// where the caller's buffer is not 16-byte aligned, and for a tile's tail).
+// Loads and stores are guarded by the point / element count of the last tile.
+template <int FMT>
+__global__ void __launch_bounds__(256) soft_demap_kernel(const double2* __restrict__ pts, long n, int k,
+                                                         double scale, void* __restrict__ out)
+{
+    constexpr int PT = 4, TILE = 256 * PT, ESZ = FMT == LLR_F32 ? 4 : 1;
+    __shared__ uint4 stage16[TILE * 8 * ESZ / 16];
+    char* stage = reinterpret_cast<char*>(stage16);
+    const int t = threadIdx.x;
+    const int m = 1 << (k / 2);
+    const double s1 = k == 1 ? 0.0 : 1.0 / (2.0 / (m - 1));
+    const SoftScale sq = soft_scale(k, scale);
+    const int gsz = k * ESZ;  // bytes per point
+    const bool vec = ((uintptr_t)out & 15) == 0;
+    const long ntiles = (n + TILE - 1) / TILE;
+    for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const long p0 = tile * TILE;
+        const int np = (int)(n - p0 < TILE ? n - p0 : TILE);  // points of this tile
+        double2 z[PT];
+#pragma unroll
+        for (int i = 0; i < PT; ++i) z[i] = t + 256 * i < np ? load_nt(pts + p0 + t + 256 * i) : make_double2(0.0, 0.0);
+#pragma unroll
+        for (int i = 0; i < PT; ++i)
+            if (t + 256 * i < np) soft_emit(z[i], k, s1, sq, FMT, stage + (t + 256 * i) * gsz, true);
+        __syncthreads();
+        char* dst = static_cast<char*>(out) + p0 * gsz;  // tiles start on 16-byte multiples of the output
+        const int nb = np * gsz;                          // bytes of this tile's output
+        const int n16 = vec ? nb >> 4 : 0;
+        for (int c = t; c < n16; c += 256) reinterpret_cast<uint4*>(dst)[c] = stage16[c];
+        if constexpr (FMT == LLR_F32) {
+            for (int e = n16 * 4 + t; e < nb / 4; e += 256)
+                reinterpret_cast<float*>(dst)[e] = reinterpret_cast<const float*>(stage)[e];
+        } else {
+            for (int e = n16 * 16 + t; e < nb; e += 256) dst[e] = stage[e];
+        }
+        __syncthreads();  // the stage is rewritten by the next tile
+    }
+}
+
 __global__ void map_kernel(const uint8_t* bytes, long nbytes, int k, const double2* table, double2* out,
                            long npts)
 {
@@ -1289,6 +1011,65 @@ hipError_t launch_demap(double2* pts, long n, int k, uint8_t* bytes, hipStream_t
     hipLaunchKernelGGL(demap_kernel, dim3((unsigned)((nbytes + bs - 1) / bs)), dim3(bs), 0, st, pts, n, k, bytes,
                        nbytes);
     return hipGetLastError();
+}
+
+hipError_t launch_soft_demap(const double2* pts, long n, int k, double scale, int fmt, void* out, hipStream_t st)
+{
+    if (n <= 0) return hipSuccess;
+    const long ntiles = (n + 1023) / 1024;
+    const long cap = 8L * num_cus();  // grid-stride: 2048 resident threads per CU
+    const unsigned grid = (unsigned)(ntiles < cap ? ntiles : cap);
+    if (fmt == LLR_F32)
+        hipLaunchKernelGGL(soft_demap_kernel<LLR_F32>, dim3(grid), dim3(256), 0, st, pts, n, k, scale, out);
+    else
+        hipLaunchKernelGGL(soft_demap_kernel<LLR_I8>, dim3(grid), dim3(256), 0, st, pts, n, k, scale, out);
+    return hipGetLastError();
+}
+
+template <int LOGN, bool STAGED, bool I16>
+static hipError_t rx_soft_launch_n(const RxArgs& a, const SoftArgs& sa, hipStream_t st)
+{
+    using FS = FftShape<LOGN>;
+    const size_t shm = rx_shm<LOGN>(a);
+    if (shm > 160 * 1024) return hipErrorInvalidValue;
+    lds_opt_in((const void*)rx_soft_kernel<LOGN, STAGED, I16>, 160 * 1024);
+    if (a.nframes <= 0) return hipSuccess;
+    // rx_launch_n's persistent grid
+    const long per_cu_w = RX_WAVES_PER_CU / (FS::T >= 64 ? FS::T / 64 : 1);
+    const long per_cu_l = (long)(160 * 1024) / (long)shm;
+    const long per_cu = per_cu_w < per_cu_l ? per_cu_w : per_cu_l;
+    const long cap = per_cu * num_cus();
+    const long grid = a.nframes < cap ? a.nframes : cap;
+    hipLaunchKernelGGL((rx_soft_kernel<LOGN, STAGED, I16>), dim3((unsigned)grid), dim3(FS::T), shm, st, a, sa);
+    return hipGetLastError();
+}
+
+// The soft rx takes every geometry of the batched rx through rx_soft_kernel
+// (never rx_wide_kernel, never the stream mode).
+template <int LOGN>
+static hipError_t rx_soft_dispatch(const RxArgs& a, const SoftArgs& sa, hipStream_t st)
+{
+    using FS = FftShape<LOGN>;
+    const bool fits = a.S <= RX_SMAX && a.D <= RX_DPT * FS::T;
+    if (a.P > FS::T || a.starts) return hipErrorInvalidValue;
+    if (!fits && a.ystage == nullptr) return hipErrorInvalidValue;
+    if (a.iq16)
+        return fits ? rx_soft_launch_n<LOGN, false, true>(a, sa, st) : rx_soft_launch_n<LOGN, true, true>(a, sa, st);
+    return fits ? rx_soft_launch_n<LOGN, false, false>(a, sa, st) : rx_soft_launch_n<LOGN, true, false>(a, sa, st);
+}
+
+hipError_t launch_rx_soft(int logn, const RxArgs& a, const SoftArgs& sa, hipStream_t st)
+{
+    switch (logn) {
+        case 6: return rx_soft_dispatch<6>(a, sa, st);
+        case 7: return rx_soft_dispatch<7>(a, sa, st);
+        case 8: return rx_soft_dispatch<8>(a, sa, st);
+        case 9: return rx_soft_dispatch<9>(a, sa, st);
+        case 10: return rx_soft_dispatch<10>(a, sa, st);
+        case 11: return rx_soft_dispatch<11>(a, sa, st);
+        case 12: return rx_soft_dispatch<12>(a, sa, st);
+        default: return hipErrorInvalidValue;
+    }
 }
 
 hipError_t launch_map(const uint8_t* bytes, long nbytes, int k, const double2* table, double2* out, hipStream_t st)

@@ -26,6 +26,7 @@ PARAM_FIELDS = [
 
 OFDM_OK = 0
 ERRORS = {-1: "INVALID", -2: "UNSUPPORTED", -3: "HIP", -4: "IO", -5: "NOMEM", -6: "PARSE"}
+LLR_F32, LLR_I8 = 0, 1  # OFDM_LLR_*: soft-decision output formats
 SYNC_CFO, SYNC_FREQ_SHIFT, SYNC_CP, SYNC_PHASE, SYNC_CHAN, SYNC_ALL = 1, 2, 4, 8, 16, 31
 
 
@@ -100,6 +101,8 @@ SIGNATURES = {
     "ofdm_rx_demod": (_I, [_V, _V, _SZ, _SZ, _V, _SZ, _V, _V, _V, _V, _V]),
     "ofdm_rx_demod_i16": (_I, [_V, _V, _SZ, _SZ, _V, _SZ, _V, _V, _V, _V, _V]),
     "ofdm_demap": (_I, [_V, _V, _SZ, _V, _V]),
+    "ofdm_soft_demap": (_I, [_V, _V, _SZ, _D, _I, _V, _V]),
+    "ofdm_rx_demod_soft": (_I, [_V, _V, _V, _SZ, _SZ, _V, _SZ, _D, _V, _I, _V, _V, _V, _V, _V, _V]),
     "ofdm_map": (_I, [_V, _V, _SZ, _V, _V]),
     "ofdm_fft_write": (_I, [_V, _V, _SZ, _V, _V]),
     "ofdm_fft_read": (_I, [_V, _V, _SZ, _V, _V]),
@@ -295,6 +298,23 @@ class Modem:
 
     def demap(self, points, n: int, bytes_out, stream=None):
         check(lib().ofdm_demap(self.h, _ptr(points), n, _ptr(bytes_out), _stream(stream)))
+
+    def soft_demap(self, points, n: int, llr_out, scale: float = 1.0, fmt: int = LLR_F32, stream=None):
+        """ofdm_soft_demap: n points -> n*k max-log LLRs (float32 or int8
+        llr_out); `points` is not modified."""
+        check(lib().ofdm_soft_demap(self.h, _ptr(points), n, scale, fmt, _ptr(llr_out), _stream(stream)))
+
+    def rx_soft(self, iq, nframes: int, llr_out, scale: float = 1.0, fmt: int = LLR_F32, frame_scale=None,
+                frame_stride: int | None = None, chan=None, chan_stride: int = 0, constell_out=None,
+                bytes_out=None, ref=None, bit_errors=None, i16: bool = False, stream=None):
+        """ofdm_rx_demod_soft: rx (f64 samples, or complex<int16> with i16)
+        that also writes nframes*npts*k LLRs; frame f's scale is
+        scale * frame_scale[f] (device doubles) where frame_scale is given."""
+        stride = self.geo.message_len if frame_stride is None else frame_stride
+        check(lib().ofdm_rx_demod_soft(self.h, None if i16 else _ptr(iq), _ptr(iq) if i16 else None, nframes, stride,
+                                       _ptr(chan), chan_stride, scale, _ptr(frame_scale), fmt, _ptr(llr_out),
+                                       _ptr(constell_out), _ptr(bytes_out), _ptr(ref), _ptr(bit_errors),
+                                       _stream(stream)))
 
     def map(self, data, nbytes: int, points_out, stream=None):
         check(lib().ofdm_map(self.h, _ptr(data), nbytes, _ptr(points_out), _stream(stream)))

@@ -220,6 +220,52 @@ int ofdm_rx_demod_read(ofdm_ctx* ctx, const double* iq, size_t nframes, size_t f
  * IN PLACE for QAM (as the reference does) and writes n*k/8 bytes (rounded up,
  * last byte left-aligned as bit_stream_converter pads). Device pointers. */
 int ofdm_demap(ofdm_ctx* ctx, double* points, size_t n, uint8_t* bytes_out, void* stream);
+/* ---- soft decisions: max-log LLRs of the reference's own constellation
+ * (modulation.cpp:4-36: natural binary per axis, not Gray), computed in FP64
+ * from the equalised point z BEFORE demod's clamp (the point constell_out
+ * holds: after the pilot gains and after the caller-side channel division).
+ * For bit b of z's k-bit symbol, MSB first (bit_stream_converter's order):
+ *
+ *   L_b = s * ( min_{c: bit_b(c)=1} |z-c|^2 - min_{c: bit_b(c)=0} |z-c|^2 )
+ *
+ * L_b > 0 means bit 0; s is the caller's scale (e.g. 1/N0). QAM is separable:
+ * the symbol is col | row*m, m = 2^(k/2); bits 0..k/2-1 come from the
+ * imaginary axis (row), bits k/2..k-1 from the real axis (col), both with PAM
+ * levels l_j = 2j/(m-1) - 1. BPSK (k = 1): L_0 = -2*sqrt(2)*(re + im)*s (its
+ * points (+-1+-j)/sqrt(2) lie on the diagonal, modulation.cpp:28-30).
+ * k = 1, 2, 4, 6, 8; any other k: OFDM_ERR_UNSUPPORTED.
+ * Output llr[point*k + b], points in constell_out order, so LLR i of a frame
+ * belongs to bit i of that frame's bytes_out stream:
+ *   OFDM_LLR_F32: (float)L_b, round to nearest (llr_out 4-byte aligned);
+ *   OFDM_LLR_I8 : (int8) clamp(rint(L_b), -127, 127), rint half-to-even on
+ *                 the FP64 value.
+ * Stores are widest where llr_out is 16-byte aligned. OFDM_ERR_INVALID: null
+ * llr_out, unknown fmt, scale not finite or <= 0, misaligned buffers.
+ * Not covered: the stream decodes (run ofdm_soft_demap on their constell_out)
+ * and the compat layer (the reference has no soft surface). */
+enum { OFDM_LLR_F32 = 0, OFDM_LLR_I8 = 1 };
+
+/* n points -> n*k LLRs. points (device, 16-byte aligned) is NOT modified
+ * (unlike ofdm_demap). */
+int ofdm_soft_demap(ofdm_ctx* ctx, const double* points, size_t n, double scale,
+                    int fmt, void* llr_out, void* stream);
+
+/* ofdm_rx_demod / ofdm_rx_demod_i16 (exactly one of iq, iq16) that also
+ * writes the LLRs of every equalised point: nframes*D*num_symb*k elements.
+ * Frame f uses s = scale * frame_scale[f] (frame_scale: nullable, device,
+ * nframes doubles, read by the kernel: a captured graph follows a changing
+ * SNR), or scale alone. constell_out, bytes_out, ref_bytes and bit_errors are
+ * ofdm_rx_demod's, with bit-identical values. Every geometry ofdm_rx_demod
+ * accepts; asynchronous; capturable. */
+int ofdm_rx_demod_soft(ofdm_ctx* ctx, const double* iq, const int16_t* iq16,
+                       size_t nframes, size_t frame_stride,
+                       const double* chan, size_t chan_stride,
+                       double scale, const double* frame_scale,
+                       int fmt, void* llr_out,
+                       double* constell_out, uint8_t* bytes_out,
+                       const uint8_t* ref_bytes, unsigned long long* bit_errors,
+                       void* stream);
+
 /* Modulation::mod alone (modulation.cpp:39-50): nbytes -> nbytes*8/k points. */
 int ofdm_map(ofdm_ctx* ctx, const uint8_t* bytes, size_t nbytes, double* points_out, void* stream);
 
