@@ -1027,6 +1027,16 @@ static int soft_args_check(const ofdm_ctx* c, double scale, int fmt, const void*
     return OFDM_OK;
 }
 
+// Channel code: kept bits of the 2*(info_bits + 6) mother bits of one codeword.
+static bool fec_rate_ok(int rate) { return rate == OFDM_FEC_R12 || rate == OFDM_FEC_R23 || rate == OFDM_FEC_R34; }
+
+static size_t fec_coded(size_t info_bits, int rate)
+{
+    const ofdm::FecRate r = ofdm::fec_rate(rate);
+    const size_t m = 2 * (info_bits + ofdm::FEC_TAIL);
+    return m / r.period * r.kept + (size_t)__builtin_popcount(r.mask & ((1u << (m % r.period)) - 1u));
+}
+
 extern "C" {
 
 int ofdm_rx_demod(ofdm_ctx* c, const double* iq, size_t nframes, size_t frame_stride, const double* chan,
@@ -1087,6 +1097,107 @@ int ofdm_rx_demod_soft(ofdm_ctx* c, const double* iq, const int16_t* iq16, size_
     ofdm::SoftArgs sa{llr_out, frame_scale, scale, fmt};
     return rx_demod_impl(c, iq, iq16, nframes, frame_stride, chan, chan_stride, constell_out, bytes_out, ref_bytes,
                          bit_errors, stream, nullptr, &sa);
+}
+
+// ---- channel code
+int ofdm_fec_coded_bits(size_t info_bits, int rate, size_t* coded_bits)
+{
+    if (!coded_bits) return fail(OFDM_ERR_INVALID, "null argument");
+    if (!fec_rate_ok(rate)) return fail(OFDM_ERR_INVALID, "rate is not OFDM_FEC_R12 / R23 / R34");
+    if (info_bits == 0 || info_bits > SIZE_MAX / 4) return fail(OFDM_ERR_INVALID, "info_bits out of range");
+    *coded_bits = fec_coded(info_bits, rate);
+    return OFDM_OK;
+}
+
+int ofdm_fec_max_info_bits(size_t capacity_bits, int rate, size_t* info_bits)
+{
+    if (!info_bits) return fail(OFDM_ERR_INVALID, "null argument");
+    if (!fec_rate_ok(rate)) return fail(OFDM_ERR_INVALID, "rate is not OFDM_FEC_R12 / R23 / R34");
+    if (capacity_bits > SIZE_MAX / 4) return fail(OFDM_ERR_INVALID, "capacity_bits out of range");
+    if (fec_coded(1, rate) > capacity_bits) return fail(OFDM_ERR_INVALID, "no codeword fits %zu bits", capacity_bits);
+    size_t lo = 1, hi = capacity_bits;  // coded_bits grows with info_bits and exceeds it: the answer is in [lo, hi]
+    while (lo < hi) {
+        const size_t mid = lo + (hi - lo + 1) / 2;
+        if (fec_coded(mid, rate) <= capacity_bits) lo = mid;
+        else hi = mid - 1;
+    }
+    *info_bits = lo;
+    return OFDM_OK;
+}
+
+int ofdm_fec_workspace_size(size_t ncw, size_t info_bits, size_t* bytes)
+{
+    if (!bytes) return fail(OFDM_ERR_INVALID, "null argument");
+    if (info_bits == 0 || info_bits > (size_t)ofdm::FEC_MAX_INFO_BITS)
+        return fail(OFDM_ERR_INVALID, "info_bits must be in [1, 2^20]");
+    const size_t words = (size_t)ofdm::fec_steps_padded((long)info_bits);
+    if (words <= (size_t)ofdm::FEC_LDS_STEPS) {
+        *bytes = 0;
+        return OFDM_OK;
+    }
+    if (ncw > SIZE_MAX / (words * 8)) return fail(OFDM_ERR_INVALID, "ncw out of range");
+    *bytes = ncw * words * 8;
+    return OFDM_OK;
+}
+
+int ofdm_fec_encode(ofdm_ctx* c, const uint8_t* info, size_t info_stride, size_t ncw, size_t info_bits, int rate,
+                    uint8_t* coded, size_t coded_stride, void* stream)
+{
+    if (!c || !info || !coded) return fail(OFDM_ERR_INVALID, "null argument");
+    if (!fec_rate_ok(rate)) return fail(OFDM_ERR_INVALID, "rate is not OFDM_FEC_R12 / R23 / R34");
+    if (info_bits == 0 || info_bits > (size_t)ofdm::FEC_MAX_INFO_BITS)
+        return fail(OFDM_ERR_INVALID, "info_bits must be in [1, 2^20]");
+    const size_t cb = fec_coded(info_bits, rate);
+    if (info_stride < (info_bits + 7) / 8) return fail(OFDM_ERR_INVALID, "info_stride below ceil(info_bits/8)");
+    if (coded_stride < (cb + 7) / 8) return fail(OFDM_ERR_INVALID, "coded_stride below ceil(coded_bits/8)");
+    if (ncw > (size_t)LONG_MAX / std::max(info_stride, coded_stride)) return fail(OFDM_ERR_INVALID, "ncw out of range");
+    if (ncw == 0) return OFDM_OK;
+    ofdm::FecEncArgs a{info, coded, (long)info_stride, (long)coded_stride, (long)ncw, (long)info_bits, (long)cb, rate};
+    hipError_t e = ofdm::launch_fec_encode(a, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "fec encode launch");
+    return OFDM_OK;
+}
+
+int ofdm_fec_decode(ofdm_ctx* c, const void* llr, int fmt, size_t llr_stride, size_t ncw, size_t info_bits, int rate,
+                    void* workspace, size_t workspace_bytes, uint8_t* info_out, size_t info_stride,
+                    const uint8_t* ref_info, unsigned long long* bit_errors, void* stream)
+{
+    if (!c || !llr || !info_out) return fail(OFDM_ERR_INVALID, "null argument");
+    if (!fec_rate_ok(rate)) return fail(OFDM_ERR_INVALID, "rate is not OFDM_FEC_R12 / R23 / R34");
+    if (fmt != OFDM_LLR_F32 && fmt != OFDM_LLR_I8) return fail(OFDM_ERR_INVALID, "fmt is not OFDM_LLR_F32 / OFDM_LLR_I8");
+    if (info_bits == 0 || info_bits > (size_t)ofdm::FEC_MAX_INFO_BITS)
+        return fail(OFDM_ERR_INVALID, "info_bits must be in [1, 2^20]");
+    if (fmt == OFDM_LLR_F32 && ((uintptr_t)llr & 3)) return fail(OFDM_ERR_INVALID, "F32 llr must be 4-byte aligned");
+    if (bit_errors && ((uintptr_t)bit_errors & 7)) return fail(OFDM_ERR_INVALID, "bit_errors must be 8-byte aligned");
+    if (llr_stride < fec_coded(info_bits, rate)) return fail(OFDM_ERR_INVALID, "llr_stride below coded_bits");
+    if (info_stride < (info_bits + 7) / 8) return fail(OFDM_ERR_INVALID, "info_stride below ceil(info_bits/8)");
+    if (ncw > (size_t)LONG_MAX / 4 / std::max(info_stride, llr_stride)) return fail(OFDM_ERR_INVALID, "ncw out of range");
+    size_t need = 0;
+    if (int rc = ofdm_fec_workspace_size(ncw, info_bits, &need)) return rc;
+    if (need) {
+        if (!workspace) return fail(OFDM_ERR_INVALID, "this length needs a workspace (ofdm_fec_workspace_size)");
+        if (!aligned16(workspace)) return fail(OFDM_ERR_INVALID, "workspace must be 16-byte aligned");
+        if (workspace_bytes < need) return fail(OFDM_ERR_INVALID, "workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    }
+    if (ncw == 0) return OFDM_OK;
+    ofdm::FecDecArgs a{};
+    a.llr = llr;
+    a.llr_stride = (long)llr_stride;
+    a.ncw = (long)ncw;
+    a.info_bits = (long)info_bits;
+    a.ws = need ? static_cast<unsigned long long*>(workspace) : nullptr;
+    a.out = info_out;
+    a.ref = ref_info;
+    a.bit_errors = bit_errors;
+    a.info_stride = (long)info_stride;
+    a.fmt = fmt;
+    a.rate = rate;
+    // OFDM_FEC_GATHER=lds: the other predecessor-gather variant (A/B measurements, tools/coded_ber.py)
+    const char* g = getenv("OFDM_FEC_GATHER");
+    a.gather = g && !strcmp(g, "lds") ? 1 : 0;
+    hipError_t e = ofdm::launch_fec_decode(a, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "fec decode launch");
+    return OFDM_OK;
 }
 
 int ofdm_map(ofdm_ctx* c, const uint8_t* bytes, size_t nbytes, double* points_out, void* stream)

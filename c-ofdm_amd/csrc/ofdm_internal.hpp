@@ -118,4 +118,45 @@ inline int tx_code_fixed(int entry) { return entry << 21; }
 // tx: persistent grid-stride launch size (symbols per workgroup = nsym / grid)
 constexpr long TX_MAX_GRID = 4096;
 
+
+// ---- channel code (ofdm_fec.hip): K=7 133/171 encoder, soft-input Viterbi
+// Puncturing of the mother stream: keep bit (i % period) of `mask`; `kept`
+// of every `period` mother bits are transmitted. The kept positions of a
+// period are 0, 1, 2 and (rate 3/4) 5.
+struct FecRate { int period, kept; unsigned mask; };
+__host__ __device__ inline FecRate fec_rate(int rate)
+{
+    return rate == 0 ? FecRate{1, 1, 0x1u} : rate == 1 ? FecRate{4, 3, 0x7u} : FecRate{6, 4, 0x27u};
+}
+constexpr int FEC_TAIL = 6;
+constexpr long FEC_MAX_INFO_BITS = 1L << 20;
+constexpr int FEC_CW_PER_WG = 4;        // one wave64 per codeword
+constexpr long FEC_LDS_STEPS = 1024;    // survivors stay in LDS up to this many (padded) trellis steps
+// trellis steps of a codeword, rounded up to the decoder's 64-step tiles (one survivor word each)
+inline long fec_steps_padded(long info_bits) { return (info_bits + FEC_TAIL + 63) & ~63L; }
+
+struct FecEncArgs {
+    const uint8_t* info;
+    uint8_t* coded;
+    long info_stride, coded_stride;   // bytes
+    long ncw, info_bits, coded_bits;
+    int rate;
+};
+
+struct FecDecArgs {
+    const void* llr;                  // float (OFDM_LLR_F32) or int8 (OFDM_LLR_I8)
+    long llr_stride;                  // elements
+    long ncw, info_bits;
+    unsigned long long* ws;           // survivors, fec_steps_padded words per codeword (LDS where null)
+    uint8_t* out;
+    const uint8_t* ref;               // nullable
+    unsigned long long* bit_errors;   // nullable
+    long info_stride;                 // bytes (out and ref)
+    int fmt, rate;
+    int gather;                       // predecessor gather: 0 ds_bpermute, 1 LDS write + 8-byte pair read
+};
+
+hipError_t launch_fec_encode(const FecEncArgs& a, hipStream_t stream);
+hipError_t launch_fec_decode(const FecDecArgs& a, hipStream_t stream);
+
 }  // namespace ofdm

@@ -27,6 +27,7 @@ PARAM_FIELDS = [
 OFDM_OK = 0
 ERRORS = {-1: "INVALID", -2: "UNSUPPORTED", -3: "HIP", -4: "IO", -5: "NOMEM", -6: "PARSE"}
 LLR_F32, LLR_I8 = 0, 1  # OFDM_LLR_*: soft-decision output formats
+FEC_R12, FEC_R23, FEC_R34 = 0, 1, 2  # OFDM_FEC_*: channel-code rates
 SYNC_CFO, SYNC_FREQ_SHIFT, SYNC_CP, SYNC_PHASE, SYNC_CHAN, SYNC_ALL = 1, 2, 4, 8, 16, 31
 
 
@@ -103,6 +104,11 @@ SIGNATURES = {
     "ofdm_demap": (_I, [_V, _V, _SZ, _V, _V]),
     "ofdm_soft_demap": (_I, [_V, _V, _SZ, _D, _I, _V, _V]),
     "ofdm_rx_demod_soft": (_I, [_V, _V, _V, _SZ, _SZ, _V, _SZ, _D, _V, _I, _V, _V, _V, _V, _V, _V]),
+    "ofdm_fec_coded_bits": (_I, [_SZ, _I, C.POINTER(_SZ)]),
+    "ofdm_fec_max_info_bits": (_I, [_SZ, _I, C.POINTER(_SZ)]),
+    "ofdm_fec_workspace_size": (_I, [_SZ, _SZ, C.POINTER(_SZ)]),
+    "ofdm_fec_encode": (_I, [_V, _V, _SZ, _SZ, _SZ, _I, _V, _SZ, _V]),
+    "ofdm_fec_decode": (_I, [_V, _V, _I, _SZ, _SZ, _SZ, _I, _V, _SZ, _V, _SZ, _V, _V, _V]),
     "ofdm_map": (_I, [_V, _V, _SZ, _V, _V]),
     "ofdm_fft_write": (_I, [_V, _V, _SZ, _V, _V]),
     "ofdm_fft_read": (_I, [_V, _V, _SZ, _V, _V]),
@@ -195,6 +201,28 @@ def config_lookup(path: str, key: str) -> int:
     v = C.c_long()
     check(lib().ofdm_config_lookup(path.encode(), key.encode(), C.byref(v)))
     return v.value
+
+
+def fec_coded_bits(info_bits: int, rate: int) -> int:
+    """ofdm_fec_coded_bits: transmitted bits of one codeword (host arithmetic)."""
+    n = C.c_size_t()
+    check(lib().ofdm_fec_coded_bits(info_bits, rate, C.byref(n)))
+    return n.value
+
+
+def fec_max_info_bits(capacity_bits: int, rate: int) -> int:
+    """ofdm_fec_max_info_bits: the largest info_bits whose codeword fits
+    capacity_bits (one codeword per frame: bytes_per_frame * 8)."""
+    n = C.c_size_t()
+    check(lib().ofdm_fec_max_info_bits(capacity_bits, rate, C.byref(n)))
+    return n.value
+
+
+def fec_workspace_size(ncw: int, info_bits: int) -> int:
+    """ofdm_fec_workspace_size: bytes of survivor storage fec_decode wants."""
+    n = C.c_size_t()
+    check(lib().ofdm_fec_workspace_size(ncw, info_bits, C.byref(n)))
+    return n.value
 
 
 def _ptr(t):
@@ -315,6 +343,33 @@ class Modem:
                                        _ptr(chan), chan_stride, scale, _ptr(frame_scale), fmt, _ptr(llr_out),
                                        _ptr(constell_out), _ptr(bytes_out), _ptr(ref), _ptr(bit_errors),
                                        _stream(stream)))
+
+    # ---- channel code (K=7 133/171, soft-input Viterbi)
+    fec_coded_bits = staticmethod(fec_coded_bits)
+    fec_max_info_bits = staticmethod(fec_max_info_bits)
+    fec_workspace_size = staticmethod(fec_workspace_size)
+
+    def fec_encode(self, info, ncw: int, info_bits: int, rate: int, coded, info_stride: int | None = None,
+                   coded_stride: int | None = None, stream=None):
+        """ofdm_fec_encode: ncw codewords of info_bits (uint8 tensors, strides
+        in bytes, minimal by default) -> coded_stride bytes each, zero-padded."""
+        istr = (info_bits + 7) // 8 if info_stride is None else info_stride
+        cstr = (fec_coded_bits(info_bits, rate) + 7) // 8 if coded_stride is None else coded_stride
+        check(lib().ofdm_fec_encode(self.h, _ptr(info), istr, ncw, info_bits, rate, _ptr(coded), cstr,
+                                    _stream(stream)))
+
+    def fec_decode(self, llr, ncw: int, info_bits: int, rate: int, info_out, fmt: int = LLR_I8,
+                   llr_stride: int | None = None, workspace=None, info_stride: int | None = None, ref=None,
+                   bit_errors=None, stream=None):
+        """ofdm_fec_decode: ncw codewords of LLRs (float32 or int8 tensor,
+        llr_stride in elements, coded_bits by default) -> ceil(info_bits/8)
+        bytes each. `workspace`: a device tensor of fec_workspace_size bytes
+        (None where that is 0)."""
+        lstr = fec_coded_bits(info_bits, rate) if llr_stride is None else llr_stride
+        istr = (info_bits + 7) // 8 if info_stride is None else info_stride
+        wbytes = workspace.numel() * workspace.element_size() if workspace is not None else 0
+        check(lib().ofdm_fec_decode(self.h, _ptr(llr), fmt, lstr, ncw, info_bits, rate, _ptr(workspace), wbytes,
+                                    _ptr(info_out), istr, _ptr(ref), _ptr(bit_errors), _stream(stream)))
 
     def map(self, data, nbytes: int, points_out, stream=None):
         check(lib().ofdm_map(self.h, _ptr(data), nbytes, _ptr(points_out), _stream(stream)))

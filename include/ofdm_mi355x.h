@@ -266,6 +266,81 @@ int ofdm_rx_demod_soft(ofdm_ctx* ctx, const double* iq, const int16_t* iq16,
                        const uint8_t* ref_bytes, unsigned long long* bit_errors,
                        void* stream);
 
+/* ---- channel code: the rate-1/2, constraint-length-7 convolutional code
+ * (generators 133/171 octal, 802.11 / DVB) with its 2/3 and 3/4 puncturings,
+ * and a soft-input Viterbi decoder fed by the LLRs above. Definition:
+ *
+ * Bits are MSB-first within bytes (bit_stream_converter's order). A codeword
+ * carries info_bits information bits u_0 .. u_{info_bits-1} followed by 6
+ * zero tail bits: T = info_bits + 6 trellis steps. The encoder state is the
+ * previous six inputs, the most recent at bit 5. At step t:
+ *     reg = (u_t << 6) | state
+ *     A_t = parity(reg & 0133),  B_t = parity(reg & 0171)
+ *     state = reg >> 1
+ * The mother stream is m[2t] = A_t, m[2t+1] = B_t (a single 1 followed by
+ * zeros gives A = 1011011, B = 1111001, weight 10). Puncturing keeps mother
+ * index i in [0, 2T) where keep[i mod period] is 1:
+ *     OFDM_FEC_R12  period 1  {1}
+ *     OFDM_FEC_R23  period 4  {1,1,1,0}
+ *     OFDM_FEC_R34  period 6  {1,1,1,0,0,1}
+ * coded_bits(info_bits, rate) is the number of kept indices; transmitted bit
+ * n of a codeword is the n-th kept mother bit.
+ *
+ * The decoder takes one LLR per transmitted bit (L > 0 means bit 0;
+ * OFDM_LLR_F32 or OFDM_LLR_I8), counts punctured positions as L = 0, and
+ * gives the information bits of the trellis path with the largest metric
+ * sum (1 - 2 c_n) L_n among the paths that start in state 0 and end in state
+ * 0 after T steps. Tie rule: new state s' has the predecessors
+ * p_j = ((2 s') & 63) | j, j = 0, 1; when both candidates are equal, j = 0
+ * survives; a candidate from a state not reachable from state 0 always loses
+ * to a reachable one. With int8 input the metrics are integers and the output
+ * is exactly defined. The decisions do not change under a positive scale of
+ * a codeword's LLRs: the soft calls' scale only sets the int8 quantisation,
+ * and frame_scale matters only to decoders that are not scale-invariant.
+ * Not covered: interleaver, scrambler, tail-biting, other codes, the stream
+ * decodes (run the decoder on LLRs from ofdm_soft_demap of their
+ * constell_out) and the compat layer (the reference has no channel code). */
+enum { OFDM_FEC_R12 = 0, OFDM_FEC_R23 = 1, OFDM_FEC_R34 = 2 };
+
+/* Host arithmetic (no context, no GPU). coded_bits of one codeword, and the
+ * largest info_bits whose coded_bits <= capacity_bits (one codeword per frame:
+ * capacity_bits = bytes_per_frame*8); OFDM_ERR_INVALID: null result, unknown
+ * rate, info_bits == 0, or no codeword fits. */
+int ofdm_fec_coded_bits(size_t info_bits, int rate, size_t* coded_bits);
+int ofdm_fec_max_info_bits(size_t capacity_bits, int rate, size_t* info_bits);
+
+/* ncw codewords, device pointers, strides in bytes (info_stride >=
+ * ceil(info_bits/8), coded_stride >= ceil(coded_bits/8)). Codeword c is read
+ * at info + c*info_stride (bits past info_bits in the last byte are ignored)
+ * and exactly coded_stride bytes are written at coded + c*coded_stride: the
+ * coded bits MSB-first, then zero bits, so coded_stride = bytes_per_frame
+ * feeds ofdm_tx_modulate directly. Asynchronous; capturable. */
+int ofdm_fec_encode(ofdm_ctx* ctx, const uint8_t* info, size_t info_stride, size_t ncw,
+                    size_t info_bits, int rate, uint8_t* coded, size_t coded_stride,
+                    void* stream);
+
+/* Bytes of survivor storage the decoder wants from the caller for ncw
+ * codewords of info_bits (0 where the survivors stay in LDS). */
+int ofdm_fec_workspace_size(size_t ncw, size_t info_bits, size_t* bytes);
+
+/* Codeword c's LLRs are llr[c*llr_stride ..] (llr_stride in elements, >=
+ * coded_bits; elements past coded_bits are not read; F32: 4-byte aligned).
+ * Writes ceil(info_bits/8) bytes at info_out + c*info_stride, the last one
+ * left-aligned and zero-padded, and nothing else. ref_info (same layout as
+ * info_out) and bit_errors (device u64, accumulated atomically as in
+ * ofdm_rx_demod) are nullable: the popcount over the info_bits bits only.
+ * workspace: device memory, 16-byte aligned, at least the size
+ * ofdm_fec_workspace_size gives; may be NULL only where that is 0. No
+ * allocation, no host copy, no synchronisation; capturable.
+ * OFDM_ERR_INVALID (both batched calls): null required pointers, unknown rate
+ * or fmt, info_bits == 0 or > 2^20, strides too small, a missing, misaligned
+ * or too-small workspace, a misaligned F32 input. ncw == 0: OFDM_OK, no
+ * launch. */
+int ofdm_fec_decode(ofdm_ctx* ctx, const void* llr, int fmt, size_t llr_stride, size_t ncw,
+                    size_t info_bits, int rate, void* workspace, size_t workspace_bytes,
+                    uint8_t* info_out, size_t info_stride, const uint8_t* ref_info,
+                    unsigned long long* bit_errors, void* stream);
+
 /* Modulation::mod alone (modulation.cpp:39-50): nbytes -> nbytes*8/k points. */
 int ofdm_map(ofdm_ctx* ctx, const uint8_t* bytes, size_t nbytes, double* points_out, void* stream);
 
