@@ -684,15 +684,38 @@ static void rx_queue_reset(ofdm_ctx* c, int* q, hipStream_t st)
     if (q) (void)hipMemsetAsync(q, 0, 2 * sizeof(int), st);
 }
 
+// True while `st` is being captured into a hipGraph. Asked only on the paths
+// that are about to allocate, copy from pageable memory or synchronise (none
+// of which a capture allows), so that they can refuse before they break the
+// capture; the launches themselves never ask.
+static bool capturing(hipStream_t st)
+{
+    hipStreamCaptureStatus s = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &s) != hipSuccess) {
+        (void)hipGetLastError();  // (the legacy stream beside another stream's capture: not capturing)
+        return false;
+    }
+    return s != hipStreamCaptureStatusNone;
+}
+
+static int capture_refused(const char* what)
+{
+    return fail(OFDM_ERR_UNSUPPORTED, "%s: not possible on a stream that is being captured (make the same call once "
+                                      "before the capture)", what);
+}
+
 // pilot_freq_sinh plan for a form of nsym symbols: S = (N+cp)*nsym = M or 5*M,
-// M = 2^m; window borders exactly as Frame.hpp:311-321 computes them.
-static int cfo_plan(ofdm_ctx* c, int nsym, ofdm_ctx::CfoPlan** out)
+// M = 2^m; window borders exactly as Frame.hpp:311-321 computes them. A new
+// form length builds and uploads its tables (allocation, host copies): `st` is
+// the stream the caller will launch on, refused while it is being captured.
+static int cfo_plan(ofdm_ctx* c, int nsym, ofdm_ctx::CfoPlan** out, hipStream_t st)
 {
     for (auto& pl : c->cfo_plans)
         if (pl.nsym == nsym) {
             *out = &pl;
             return OFDM_OK;
         }
+    if (capturing(st)) return capture_refused("the tables of a new CFO form length");
     const long S = (long)c->L * nsym;
     ofdm_ctx::CfoPlan pl;
     pl.nsym = nsym;
@@ -996,6 +1019,7 @@ static int rx_demod_impl(ofdm_ctx* c, const double* iq, const int16_t* iq16, siz
         } else {
             const size_t need = nframes * (size_t)c->S * c->D * sizeof(double2);
             if (need > c->scratch_bytes) {
+                if (capturing((hipStream_t)stream)) return capture_refused("growing the staged rx scratch");
                 HIP_TRY(hipSetDevice(c->device));
                 if (c->d_scratch) HIP_TRY(hipFree(c->d_scratch));
                 c->d_scratch = nullptr;
@@ -1343,6 +1367,8 @@ int ofdm_preamble_corr(ofdm_ctx* c, const double* iq, size_t n, long start, doub
     if (!c || !iq || !cor_out) return fail(OFDM_ERR_INVALID, "null argument");
     if (!aligned16(iq)) return fail(OFDM_ERR_INVALID, "iq must be 16-byte aligned");
     if (start < INT32_MIN || start > INT32_MAX) return fail(OFDM_ERR_INVALID, "start out of range");
+    if (capturing((hipStream_t)stream))
+        return capture_refused("ofdm_preamble_corr (it stages `start` from the host and synchronises)");
     int* d_start = c->d_first + 2;  // scratch word 2: the one start index
     const int s32 = (int)start;
     HIP_TRY(hipMemcpyAsync(d_start, &s32, sizeof(int), hipMemcpyHostToDevice, (hipStream_t)stream));
@@ -1372,7 +1398,7 @@ int ofdm_cfo_estimate(ofdm_ctx* c, const double* x, size_t nframes, size_t strid
     if (!aligned16(x)) return fail(OFDM_ERR_INVALID, "x must be 16-byte aligned");
     if (nframes == 0) return OFDM_OK;
     ofdm_ctx::CfoPlan* pl = nullptr;
-    int rc = cfo_plan(c, nsym, &pl);
+    int rc = cfo_plan(c, nsym, &pl, (hipStream_t)stream);
     if (rc) return rc;
     ofdm::CfoArgs a{};
     a.x = reinterpret_cast<const double2*>(x);
@@ -1500,6 +1526,8 @@ int ofdm_sync_frames(ofdm_ctx* c, double* frames, size_t nframes, size_t stride,
         double* dst = cfo_out;
         if (!dst) {
             if (c->cfo_scratch_n < nframes) {
+                if (capturing((hipStream_t)stream))
+                    return capture_refused("growing the CFO scratch (cfo_out = NULL)");
                 HIP_TRY(hipSetDevice(c->device));
                 if (c->d_cfo_scratch) HIP_TRY(hipFree(c->d_cfo_scratch));
                 c->d_cfo_scratch = nullptr;
@@ -1757,7 +1785,7 @@ static int rx_stream_impl(ofdm_ctx* c, const double* iq, const int16_t* iq16, si
     const bool fused = c->S <= ofdm::RX_SMAX && c->D <= ofdm::RX_DPT * (c->N / 8) && c->P <= c->N / 8 &&
                        c->npr == 1 && c->S + 1 <= 64 && c->L % (c->N / 8) == 0 && c->L / (c->N / 8) <= 16 &&
                        c->cp <= 2 * (c->N / 8) &&  // stream_params_kernel: CP template in 2 registers
-                       cfo_plan(c, c->npr, &pl) == OFDM_OK;
+                       cfo_plan(c, c->npr, &pl, st) == OFDM_OK;
     const size_t per = (size_t)c->D * sizeof(double2) + (size_t)c->S * ofdm::CORR_PER_SYM * sizeof(double2) + sizeof(double);
     const long npts = (long)c->D * c->S;
     // frames [0, nb) of d_list (device count d_cnt, if set, bounds them further)

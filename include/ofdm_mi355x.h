@@ -15,8 +15,33 @@
  *     layout of the reference and of its data/<name>.bin files).
  *   - Batched compute entry points take DEVICE pointers and an explicit HIP
  *     stream passed as void* (NULL = the legacy default stream). They are
- *     asynchronous; they never allocate, copy to the host or synchronise, so
- *     they can be captured into a hipGraph.
+ *     asynchronous.
+ *   - Graph capture. The batched compute calls (tx_modulate, tx_frames,
+ *     rx_demod and its _i16 / _read / _soft forms, map, demap, soft_demap,
+ *     fec_encode, fec_decode, fft_write, fft_read, bit_convert,
+ *     int16_to_double, double_to_int16, t2_scan, find_preamble, cfo_estimate,
+ *     freq_shift, cp_sync, phase_sync, sync_chain, chan_estimate, sync_frames)
+ *     and ofdm_copy only launch kernels on `stream`: no
+ *     allocation, no host copy, no synchronisation, and every per-launch
+ *     device counter is left as the next launch needs it. A chain of them can
+ *     be captured into a hipGraph on one stream and replayed
+ *     (tests/test_gpu_graph.py). Three of them allocate context scratch the
+ *     first time a context sees a size, so make the same call once before
+ *     the capture:
+ *       - ofdm_rx_demod* without constell_out on a staged geometry
+ *         (num_symb > 8): a scratch of nframes frames, grown when a call asks
+ *         for more frames than any call before it;
+ *       - ofdm_sync_frames with OFDM_SYNC_CFO and cfo_out = NULL: nframes
+ *         doubles, grown likewise;
+ *       - ofdm_cfo_estimate / ofdm_sync_frames on a form length (nsym) the
+ *         context has not seen: its tables are built and uploaded.
+ *     On a stream that is being captured these first calls return
+ *     OFDM_ERR_UNSUPPORTED before anything is issued (the capture stays
+ *     valid). Not capturable: ofdm_preamble_corr (it stages `start` from the
+ *     host and synchronises the stream; OFDM_ERR_UNSUPPORTED on a capturing
+ *     stream), ofdm_rx_stream* (the host waits for the walk's status word),
+ *     ofdm_reduce_counters, and the memcpy / synchronize / event helpers,
+ *     which are plain HIP calls with HIP's own capture rules.
  *   - One ofdm_ctx per thread (or per GPU); a ctx is not re-entrant, matching
  *     the reference (one FRAME_FORM per thread).
  *   - Streams: rx launches keep their frame-queue counter per HIP stream, so
@@ -256,7 +281,8 @@ int ofdm_soft_demap(ofdm_ctx* ctx, const double* points, size_t n, double scale,
  * nframes doubles, read by the kernel: a captured graph follows a changing
  * SNR), or scale alone. constell_out, bytes_out, ref_bytes and bit_errors are
  * ofdm_rx_demod's, with bit-identical values. Every geometry ofdm_rx_demod
- * accepts; asynchronous; capturable. */
+ * accepts; asynchronous; capturable (a staged geometry without constell_out
+ * after one call outside the capture, as ofdm_rx_demod). */
 int ofdm_rx_demod_soft(ofdm_ctx* ctx, const double* iq, const int16_t* iq16,
                        size_t nframes, size_t frame_stride,
                        const double* chan, size_t chan_stride,
@@ -388,7 +414,10 @@ int ofdm_find_preamble(ofdm_ctx* ctx, const double* iq, size_t n,
 
 /* PREAMBLE_FORM::find_corr (Frame.cpp:297-335): the normalised correlation
  * at every lag from `start` (cor_out[i] = |sum x[start+i+j] c_j| / sqrt(norm_i)
- * where norm_i > 1, else 0; 2*T2sin_size + pr_sin_len lags). Device arrays. */
+ * where norm_i > 1, else 0; 2*T2sin_size + pr_sin_len lags). Device arrays.
+ * Samples past n read as 0. Unlike the other compute calls this one copies
+ * `start` from the host and synchronises `stream` before it returns: it cannot
+ * be captured (OFDM_ERR_UNSUPPORTED on a capturing stream). */
 int ofdm_preamble_corr(ofdm_ctx* ctx, const double* iq, size_t n, long start, double* cor_out,
                        void* stream);
 
@@ -443,7 +472,12 @@ int ofdm_chan_estimate(ofdm_ctx* ctx, const double* x, size_t nframes, size_t fr
 /* The main.cpp:60-66 chain on each frame's message_with_preamble region
  * (preamble + message, in place): cfo -> freq_shift -> cp_sync -> phase_sync
  * (context preamble) -> chan_estimate. Clear OFDM_SYNC_* bits to skip a stage
- * (cfo_in, nullable, then supplies the CFO). Outputs nullable. */
+ * (cfo_in, nullable, then supplies the CFO; OFDM_SYNC_FREQ_SHIFT with neither
+ * OFDM_SYNC_CFO nor cfo_in: OFDM_ERR_INVALID, nothing launched). Outputs
+ * nullable: without cfo_out the estimate goes to a context scratch (allocated
+ * by the first call of a given nframes: see "Graph capture" above); without
+ * chan_out OFDM_SYNC_CHAN does nothing. Each stage equals its stand-alone call
+ * bit for bit. */
 enum {
     OFDM_SYNC_CFO = 1, OFDM_SYNC_FREQ_SHIFT = 2, OFDM_SYNC_CP = 4,
     OFDM_SYNC_PHASE = 8, OFDM_SYNC_CHAN = 16, OFDM_SYNC_ALL = 31
