@@ -1061,6 +1061,35 @@ static size_t fec_coded(size_t info_bits, int rate)
     return m / r.period * r.kept + (size_t)__builtin_popcount(r.mask & ((1u << (m % r.period)) - 1u));
 }
 
+// Interleaver: a block of n positions in c columns with rotation group s.
+static bool il_params_ok(size_t n, size_t c, size_t s)
+{
+    return n >= 8 && n <= (size_t)ofdm::IL_MAX_BLOCK && n % 8 == 0 && c >= 1 && n % c == 0 && s >= 1 &&
+           (n / c) % s == 0;
+}
+
+// The three interleave entry points: `kind` is ofdm::IL_BITS / IL_I8 / IL_F32.
+static int interleave_impl(ofdm_ctx* c, const void* in, int kind, size_t nblocks, size_t n, size_t cols, size_t s,
+                           int dir, void* out, void* stream)
+{
+    if (!c || !in || !out) return fail(OFDM_ERR_INVALID, "null argument");
+    if (!il_params_ok(n, cols, s))
+        return fail(OFDM_ERR_INVALID, "block_bits=%zu, cols=%zu, s=%zu is no valid interleaver block", n, cols, s);
+    if (dir != OFDM_IL_FORWARD && dir != OFDM_IL_INVERSE)
+        return fail(OFDM_ERR_INVALID, "dir is not OFDM_IL_FORWARD / OFDM_IL_INVERSE");
+    if (kind == ofdm::IL_F32 && (((uintptr_t)in | (uintptr_t)out) & 3))
+        return fail(OFDM_ERR_INVALID, "F32 buffers must be 4-byte aligned");
+    if (nblocks > (size_t)LONG_MAX / (4 * n)) return fail(OFDM_ERR_INVALID, "nblocks out of range");
+    const size_t bytes = kind == ofdm::IL_BITS ? nblocks * n / 8 : kind == ofdm::IL_I8 ? nblocks * n : nblocks * n * 4;
+    const uintptr_t a0 = (uintptr_t)in, b0 = (uintptr_t)out;
+    if (a0 < b0 + bytes && b0 < a0 + bytes && bytes) return fail(OFDM_ERR_INVALID, "in and out overlap");
+    if (nblocks == 0) return OFDM_OK;
+    ofdm::IlArgs a{in, out, (long)nblocks, (int)n, (int)cols, (int)s, kind, dir};
+    hipError_t e = ofdm::launch_interleave(a, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "interleave launch");
+    return OFDM_OK;
+}
+
 extern "C" {
 
 int ofdm_rx_demod(ofdm_ctx* c, const double* iq, size_t nframes, size_t frame_stride, const double* chan,
@@ -1221,6 +1250,50 @@ int ofdm_fec_decode(ofdm_ctx* c, const void* llr, int fmt, size_t llr_stride, si
     a.gather = g && !strcmp(g, "lds") ? 1 : 0;
     hipError_t e = ofdm::launch_fec_decode(a, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "fec decode launch");
+    return OFDM_OK;
+}
+
+// ---- interleaver and scrambler
+int ofdm_interleave_default(const ofdm_ctx* c, size_t* block_bits, size_t* cols, size_t* s)
+{
+    if (!c || !block_bits || !cols || !s) return fail(OFDM_ERR_INVALID, "null argument");
+    const size_t n = (size_t)c->D * (size_t)c->k, rot = c->k >= 2 ? (size_t)c->k / 2 : 1;
+    if (!il_params_ok(n, 16, rot))
+        return fail(OFDM_ERR_UNSUPPORTED, "num_data_subc*modType = %zu bits is no valid block of 16 columns", n);
+    *block_bits = n;
+    *cols = 16;
+    *s = rot;
+    return OFDM_OK;
+}
+
+int ofdm_interleave_bits(ofdm_ctx* c, const uint8_t* in, size_t nblocks, size_t block_bits, size_t cols, size_t s,
+                         int dir, uint8_t* out, void* stream)
+{
+    return interleave_impl(c, in, ofdm::IL_BITS, nblocks, block_bits, cols, s, dir, out, stream);
+}
+
+int ofdm_interleave_llr(ofdm_ctx* c, const void* in, int fmt, size_t nblocks, size_t block_bits, size_t cols,
+                        size_t s, int dir, void* out, void* stream)
+{
+    if (fmt != OFDM_LLR_F32 && fmt != OFDM_LLR_I8) return fail(OFDM_ERR_INVALID, "fmt is not OFDM_LLR_F32 / OFDM_LLR_I8");
+    return interleave_impl(c, in, fmt == OFDM_LLR_F32 ? ofdm::IL_F32 : ofdm::IL_I8, nblocks, block_bits, cols, s, dir,
+                           out, stream);
+}
+
+int ofdm_scramble(ofdm_ctx* c, const uint8_t* in, size_t in_stride, size_t ncw, size_t nbits, unsigned seed,
+                  const uint8_t* seeds, uint8_t* out, size_t out_stride, void* stream)
+{
+    if (!c || !in || !out) return fail(OFDM_ERR_INVALID, "null argument");
+    if (nbits == 0 || nbits > (size_t)LONG_MAX / 2) return fail(OFDM_ERR_INVALID, "nbits out of range");
+    const size_t nbytes = (nbits + 7) / 8;
+    if (in_stride < nbytes || out_stride < nbytes) return fail(OFDM_ERR_INVALID, "stride below ceil(nbits/8)");
+    if (!seeds && (seed < 1 || seed > 127)) return fail(OFDM_ERR_INVALID, "seed %u is not in 1..127", seed);
+    if (in == out && in_stride != out_stride) return fail(OFDM_ERR_INVALID, "in place needs equal strides");
+    if (ncw > (size_t)LONG_MAX / std::max(in_stride, out_stride)) return fail(OFDM_ERR_INVALID, "ncw out of range");
+    if (ncw == 0) return OFDM_OK;
+    ofdm::ScrArgs a{in, out, seeds, (long)in_stride, (long)out_stride, (long)ncw, (long)nbits, seed};
+    hipError_t e = ofdm::launch_scramble(a, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "scramble launch");
     return OFDM_OK;
 }
 

@@ -159,4 +159,30 @@ struct FecDecArgs {
 hipError_t launch_fec_encode(const FecEncArgs& a, hipStream_t stream);
 hipError_t launch_fec_decode(const FecDecArgs& a, hipStream_t stream);
 
+
+// ---- interleaver and scrambler (ofdm_interleave.hip)
+constexpr long IL_MAX_BLOCK = 32768;    // positions of one block
+enum { IL_BITS = 0, IL_I8 = 1, IL_F32 = 2 };
+
+struct IlArgs {
+    const void* in;
+    void* out;
+    long nblocks;
+    int n, c, s;                      // block positions, columns, rotation group (validated by the caller)
+    int kind;                         // IL_BITS (MSB-first packed bits), IL_I8, IL_F32
+    int dir;                          // 0 forward, 1 inverse
+};
+
+struct ScrArgs {
+    const uint8_t* in;
+    uint8_t* out;
+    const uint8_t* seeds;             // nullable: one seed per codeword
+    long in_stride, out_stride;       // bytes
+    long ncw, nbits;
+    unsigned seed;                    // 1..127, used where seeds is null
+};
+
+hipError_t launch_interleave(const IlArgs& a, hipStream_t stream);
+hipError_t launch_scramble(const ScrArgs& a, hipStream_t stream);
+
 }  // namespace ofdm

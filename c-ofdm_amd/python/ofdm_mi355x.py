@@ -28,6 +28,7 @@ OFDM_OK = 0
 ERRORS = {-1: "INVALID", -2: "UNSUPPORTED", -3: "HIP", -4: "IO", -5: "NOMEM", -6: "PARSE"}
 LLR_F32, LLR_I8 = 0, 1  # OFDM_LLR_*: soft-decision output formats
 FEC_R12, FEC_R23, FEC_R34 = 0, 1, 2  # OFDM_FEC_*: channel-code rates
+IL_FORWARD, IL_INVERSE = 0, 1  # OFDM_IL_*: interleaver directions
 SYNC_CFO, SYNC_FREQ_SHIFT, SYNC_CP, SYNC_PHASE, SYNC_CHAN, SYNC_ALL = 1, 2, 4, 8, 16, 31
 
 
@@ -109,6 +110,10 @@ SIGNATURES = {
     "ofdm_fec_workspace_size": (_I, [_SZ, _SZ, C.POINTER(_SZ)]),
     "ofdm_fec_encode": (_I, [_V, _V, _SZ, _SZ, _SZ, _I, _V, _SZ, _V]),
     "ofdm_fec_decode": (_I, [_V, _V, _I, _SZ, _SZ, _SZ, _I, _V, _SZ, _V, _SZ, _V, _V, _V]),
+    "ofdm_interleave_default": (_I, [_V, C.POINTER(_SZ), C.POINTER(_SZ), C.POINTER(_SZ)]),
+    "ofdm_interleave_bits": (_I, [_V, _V, _SZ, _SZ, _SZ, _SZ, _I, _V, _V]),
+    "ofdm_interleave_llr": (_I, [_V, _V, _I, _SZ, _SZ, _SZ, _SZ, _I, _V, _V]),
+    "ofdm_scramble": (_I, [_V, _V, _SZ, _SZ, _SZ, C.c_uint, _V, _V, _SZ, _V]),
     "ofdm_map": (_I, [_V, _V, _SZ, _V, _V]),
     "ofdm_fft_write": (_I, [_V, _V, _SZ, _V, _V]),
     "ofdm_fft_read": (_I, [_V, _V, _SZ, _V, _V]),
@@ -370,6 +375,42 @@ class Modem:
         wbytes = workspace.numel() * workspace.element_size() if workspace is not None else 0
         check(lib().ofdm_fec_decode(self.h, _ptr(llr), fmt, lstr, ncw, info_bits, rate, _ptr(workspace), wbytes,
                                     _ptr(info_out), istr, _ptr(ref), _ptr(bit_errors), _stream(stream)))
+
+    # ---- interleaver and scrambler
+    def interleave_default(self) -> tuple[int, int, int]:
+        """ofdm_interleave_default: (block_bits, cols, s) of the context's
+        per-symbol block."""
+        n, c, s = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        check(lib().ofdm_interleave_default(self.h, C.byref(n), C.byref(c), C.byref(s)))
+        return n.value, c.value, s.value
+
+    def _il_block(self, block):
+        return self.interleave_default() if block is None else block
+
+    def interleave_bits(self, data, nblocks: int, out, direction: int = IL_FORWARD, block=None, stream=None):
+        """ofdm_interleave_bits: nblocks blocks of MSB-first bits (uint8
+        tensors that do not overlap); `block` is (block_bits, cols, s),
+        interleave_default() where None."""
+        n, c, s = self._il_block(block)
+        check(lib().ofdm_interleave_bits(self.h, _ptr(data), nblocks, n, c, s, direction, _ptr(out), _stream(stream)))
+
+    def interleave_llr(self, llr, nblocks: int, out, direction: int = IL_INVERSE, fmt: int = LLR_I8, block=None,
+                       stream=None):
+        """ofdm_interleave_llr: the same permutation on float32 or int8
+        elements, moved bit for bit."""
+        n, c, s = self._il_block(block)
+        check(lib().ofdm_interleave_llr(self.h, _ptr(llr), fmt, nblocks, n, c, s, direction, _ptr(out),
+                                        _stream(stream)))
+
+    def scramble(self, data, ncw: int, nbits: int, out, seed: int = 127, seeds=None, in_stride: int | None = None,
+                 out_stride: int | None = None, stream=None):
+        """ofdm_scramble: ncw codewords of nbits XORed with the x^7 + x^4 + 1
+        sequence of `seed` (or of the device bytes `seeds`, one per codeword);
+        strides in bytes, minimal by default; out may be data itself."""
+        nbytes = (nbits + 7) // 8
+        check(lib().ofdm_scramble(self.h, _ptr(data), nbytes if in_stride is None else in_stride, ncw, nbits, seed,
+                                  _ptr(seeds), _ptr(out), nbytes if out_stride is None else out_stride,
+                                  _stream(stream)))
 
     def map(self, data, nbytes: int, points_out, stream=None):
         check(lib().ofdm_map(self.h, _ptr(data), nbytes, _ptr(points_out), _stream(stream)))

@@ -18,7 +18,7 @@
  *     asynchronous.
  *   - Graph capture. The batched compute calls (tx_modulate, tx_frames,
  *     rx_demod and its _i16 / _read / _soft forms, map, demap, soft_demap,
- *     fec_encode, fec_decode, fft_write, fft_read, bit_convert,
+ *     fec_encode, fec_decode, interleave_bits, interleave_llr, scramble, fft_write, fft_read, bit_convert,
  *     int16_to_double, double_to_int16, t2_scan, find_preamble, cfo_estimate,
  *     freq_shift, cp_sync, phase_sync, sync_chain, chan_estimate, sync_frames)
  *     and ofdm_copy only launch kernels on `stream`: no
@@ -323,7 +323,7 @@ int ofdm_rx_demod_soft(ofdm_ctx* ctx, const double* iq, const int16_t* iq16,
  * is exactly defined. The decisions do not change under a positive scale of
  * a codeword's LLRs: the soft calls' scale only sets the int8 quantisation,
  * and frame_scale matters only to decoders that are not scale-invariant.
- * Not covered: interleaver, scrambler, tail-biting, other codes, the stream
+ * Not covered: tail-biting, other codes, the stream
  * decodes (run the decoder on LLRs from ofdm_soft_demap of their
  * constell_out) and the compat layer (the reference has no channel code). */
 enum { OFDM_FEC_R12 = 0, OFDM_FEC_R23 = 1, OFDM_FEC_R34 = 2 };
@@ -366,6 +366,74 @@ int ofdm_fec_decode(ofdm_ctx* ctx, const void* llr, int fmt, size_t llr_stride, 
                     size_t info_bits, int rate, void* workspace, size_t workspace_bytes,
                     uint8_t* info_out, size_t info_stride, const uint8_t* ref_info,
                     unsigned long long* bit_errors, void* stream);
+
+/* ---- interleaver and scrambler: the two stages between the channel code
+ * and the modem. The device-side chain is
+ *     tx: ofdm_scramble, ofdm_fec_encode, ofdm_interleave_bits (forward),
+ *         ofdm_tx_modulate
+ *     rx: ofdm_rx_demod_soft, ofdm_interleave_llr (inverse), ofdm_fec_decode,
+ *         ofdm_scramble
+ * (INTEGRATION.md has the arguments). Every call below that takes a stream is
+ * batched, takes device pointers and only launches kernels: no allocation,
+ * no host copy, no synchronisation; capturable.
+ *
+ * The permutation. A block has n = block_bits positions, c = cols columns
+ * and a rotation group s. Block position q (0 <= q < n) moves to
+ *     i = (n/c) * (q mod c) + floor(q / c)
+ *     j = s * floor(i/s) + (i + n - floor(c*i / n)) mod s
+ * OFDM_IL_FORWARD writes out[j(q)] = in[q], OFDM_IL_INVERSE out[q] = in[j(q)].
+ * The inverse map in closed form:
+ *     i = s*floor(j/s) + (j + floor(c*j/n)) mod s
+ *     q = c*i - (n-1)*floor(c*i/n)
+ * Valid: c >= 1, c | n, s >= 1, s | (n/c), n % 8 == 0, 8 <= n <= 32768. With
+ * c = 16 and s = max(k/2, 1) this is the 802.11a interleaver: (48, 16, 1)
+ * starts 0, 3, 6, 9, ..., (192, 16, 2) starts 0, 13, 24, 37, 48, 61, ....
+ * A frame's blocks are its OFDM symbols, n = num_data_subc * modType; the pad
+ * bits behind a frame's codeword are interleaved with everything else.
+ *
+ * The scrambler is additive, x^7 + x^4 + 1: s_t = s_{t-4} ^ s_{t-7}, with
+ * s_{-m} = bit m-1 of the seed for m = 1..7; out bit t = in bit t ^ s_t (bits
+ * MSB-first). Seed 127 gives the 802.11 sequence 00001110 11110010 11001001
+ * 00000010 ..., period 127. The operation is its own inverse.
+ *
+ * OFDM_ERR_INVALID (the batched calls): null required pointers, invalid
+ * (n, c, s), unknown dir or fmt, strides too small, nbits == 0, a scalar seed
+ * outside 1..127, misaligned F32, in and out overlapping (ofdm_scramble: in ==
+ * out with other than equal strides). nblocks == 0 or ncw == 0: OFDM_OK, no
+ * launch. A grid that does not fit: OFDM_ERR_HIP, nothing launched.
+ * Not covered: the deinterleave fused into the decoder or the soft rx, a CRC,
+ * per-carrier weighting of the LLRs, and the compat layer. */
+enum { OFDM_IL_FORWARD = 0, OFDM_IL_INVERSE = 1 };
+
+/* Host arithmetic: the context's per-symbol block, num_data_subc*modType
+ * positions in 16 columns with s = max(modType/2, 1). OFDM_ERR_UNSUPPORTED
+ * where those are no valid parameters. */
+int ofdm_interleave_default(const ofdm_ctx* ctx, size_t* block_bits, size_t* cols, size_t* s);
+
+/* nblocks blocks of MSB-first bits, nblocks*block_bits/8 bytes each side. in
+ * and out must not overlap; in is not modified. Forward on ofdm_fec_encode's
+ * output (coded_stride = bytes_per_frame, nblocks = nframes*num_symb) feeds
+ * ofdm_tx_modulate; inverse on the hard rx's bytes_out gives the
+ * hard-decision path. */
+int ofdm_interleave_bits(ofdm_ctx* ctx, const uint8_t* in, size_t nblocks, size_t block_bits,
+                         size_t cols, size_t s, int dir, uint8_t* out, void* stream);
+
+/* The same permutation on elements (fmt: OFDM_LLR_F32, 4-byte aligned, or
+ * OFDM_LLR_I8, any address), moved bit for bit: NaN payloads and -0.0 come
+ * through unchanged. Loads and stores are widest where both buffers are
+ * 16-byte aligned. Inverse on ofdm_rx_demod_soft's llr_out with
+ * nblocks = nframes*num_symb gives the layout ofdm_fec_decode takes with
+ * llr_stride = bytes_per_frame*8. */
+int ofdm_interleave_llr(ofdm_ctx* ctx, const void* in, int fmt, size_t nblocks, size_t block_bits,
+                        size_t cols, size_t s, int dir, void* out, void* stream);
+
+/* ncw codewords of nbits, strides in bytes (>= ceil(nbits/8)). Writes exactly
+ * ceil(nbits/8) bytes per codeword; the bits past nbits in the last one are
+ * written 0. seed in 1..127; seeds (nullable, device, ncw bytes) gives one
+ * seed per codeword instead, a value v outside 1..127 counting as
+ * ((v-1) mod 127) + 1. in == out with equal strides is allowed. */
+int ofdm_scramble(ofdm_ctx* ctx, const uint8_t* in, size_t in_stride, size_t ncw, size_t nbits,
+                  unsigned seed, const uint8_t* seeds, uint8_t* out, size_t out_stride, void* stream);
 
 /* Modulation::mod alone (modulation.cpp:39-50): nbytes -> nbytes*8/k points. */
 int ofdm_map(ofdm_ctx* ctx, const uint8_t* bytes, size_t nbytes, double* points_out, void* stream);
