@@ -98,10 +98,12 @@ __device__ __forceinline__ double2 cmul_exact(double2 a, double2 b)
 // atan2 for the stream decode's phases (carg of a complex sum: cp_freq_sinh,
 // pr_phase_sinh, chan_char_lq's per-carrier angles; Frame.hpp:238-274,
 // 397-405), within 3 ulp of the correctly rounded value (the stream's 1e-9
-// parity bar; measured 2.5 ulp worst over 2e5 random arguments against a
-// 50-digit atan2), branch-free, about 45 VALU instructions against the math
-// library's ~105. Octant reduction to |u| <= tan(pi/8) with one division
-// (u = n/d, or (n - d)/(n + d) and pi/4 added), then atan(u) = u + u z P(z),
+// parity bar; measured 2 ulp worst over 2e5 arguments against a 60-digit
+// atan2 rounded to double: tests/test_gpu_devtest.py), branch-free, about 50
+// VALU instructions against the math library's ~105. Octant reduction to
+// |u| <= tan(pi/8) with one division (u = n/d, or (n - d)/(n + d) and pi/4
+// added; n and d scaled first at both ends of the range), then
+// atan(u) = u + u z P(z),
 // z = u^2, P of degree 10 (a Chebyshev-node fit with 2e-18 absolute error
 // on [0, tan^2(pi/8)]). IEEE special cases by selects: zeros (+-0 or +-pi
 // by the signs), infinities (multiples of pi/4), NaN.
@@ -114,8 +116,13 @@ __device__ __forceinline__ double atan2_fast(double y, double x)
         ay = iy ? 1.0 : 0.0;
     }
     const bool sw = ay > ax;
-    const double n = sw ? ax : ay, d0 = sw ? ay : ax;  // n <= d
-    const double d = d0 > 0.0 ? d0 : 1.0;              // both zero: u = 0
+    const double n0 = sw ? ax : ay, d0 = sw ? ay : ax;  // n <= d
+    // exact power-of-two scaling at the ends of the range: n + d must not
+    // overflow, and a subnormal d would round d * tan(pi/8) to a few bits
+    // (2/4 of the least subnormal took the n / d branch with u = 0.5)
+    const double sc = d0 > 0x1p1022 ? 0.5 : (d0 < 0x1p-1022 ? 0x1p108 : 1.0);
+    const double n = n0 * sc;
+    const double d = d0 > 0.0 ? d0 * sc : 1.0;          // both zero: u = 0
     const bool hi = n > d * 0.41421356237309503;       // tan(pi/8)
     const double u = hi ? (n - d) / (n + d) : n / d;
     const double z = u * u;

@@ -1,0 +1,302 @@
+"""The two device primitives of chan_char_lq's phase path, called directly
+through the test-only library (c-ofdm_amd/devtest, tests/devtest.py):
+
+atan2_fast against mpmath.atan2 at 60 digits rounded to double, within the 3
+ulp the header claims, over arguments chosen one at a time (huge, tiny and
+subnormal magnitudes, the octant-reduction edge, ratios near 0 and 1, every
+sign combination, the IEEE special cases); cp_phase's all-zero sums.
+
+unwrap_scan<NT, WAVE> against the serial one-pass loop in float64, bit for
+bit, for every instantiated form and lengths around the thread, wave and
+R-entries-per-thread boundaries, on inputs that make the scan's maps
+non-trivial: exact +-pi ties included, which no sample-level input produces."""
+from fractions import Fraction
+
+import mpmath
+import numpy as np
+import pytest
+
+import devtest
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+
+ULP_BAR = 3  # ofdm_fft.hpp: "within 3 ulp of the correctly rounded value"
+TAN_PI_8 = 0.41421356237309503  # the kernel's octant-reduction constant
+
+
+# ---------------------------------------------------------------- atan2_fast
+def _mp_to_double(v) -> float:
+    """Correctly rounded double of an mpf (subnormal results included:
+    int / int true division rounds once)."""
+    s, m, e, bc = v._mpf_
+    if m == 0:
+        return 0.0
+    if e + bc > -1000:  # a normal double: mpmath rounds the mantissa to 53 bits once
+        return float(mpmath.mpf(v._mpf_))
+    f = Fraction(int(m)) * Fraction(2) ** int(e)
+    return float(-f if s else f)
+
+
+def _reference(ay, ax):
+    """atan2 for the four sign combinations of each (|y|, |x|) pair: one
+    60-digit atan2 per pair, the other quadrants by pi - a in the same
+    precision. Returns (y, x, ref) with 4 len(ay) entries."""
+    mpmath.mp.dps = 60
+    pi = mpmath.mp.pi
+    ys, xs, ref = [], [], []
+    for a, b in zip(ay.tolist(), ax.tolist()):
+        q = mpmath.atan2(mpmath.mpf(a), mpmath.mpf(b))
+        r1, r2 = _mp_to_double(q), _mp_to_double(pi - q)
+        ys += [a, a, -a, -a]
+        xs += [b, -b, b, -b]
+        ref += [r1, r2, -r1, -r2]
+    return np.array(ys), np.array(xs), np.array(ref)
+
+
+def _ordered(a):
+    """Doubles as integers whose difference counts representable values."""
+    i = np.asarray(a, np.float64).view(np.int64)
+    return np.where(i < 0, np.int64(-2 ** 63) - i, i).astype(np.longdouble)
+
+
+def _ulps(got, ref):
+    return np.abs(_ordered(got) - _ordered(ref))
+
+
+def _magnitude_pairs():
+    rng = np.random.default_rng(20240)
+    out = []
+
+    def add(ay, ax):
+        out.append((np.abs(np.asarray(ay, np.float64)), np.abs(np.asarray(ax, np.float64))))
+
+    # random directions at magnitudes 1e-300 .. 1e300 (first quadrant; signs below)
+    n = 24000
+    th = rng.uniform(0, np.pi / 2, n)
+    mag = 10.0 ** rng.uniform(-300, 300, n)
+    add(mag * np.sin(th), mag * np.cos(th))
+    # independent magnitudes: ratios from 1e-600 to 1e600
+    n = 4000
+    add(10.0 ** rng.uniform(-300, 300, n), 10.0 ** rng.uniform(-300, 300, n))
+    # the top binades, where n + d overflows unless the kernel scales
+    n = 3000
+    add(rng.uniform(0.25, 1.0, n) * np.finfo(np.float64).max, rng.uniform(0.25, 1.0, n) * np.finfo(np.float64).max)
+    add([0.9e308, 1e308, np.finfo(np.float64).max, 2.0 ** 1022, np.nextafter(2.0 ** 1022, np.inf), 2.0 ** 1023],
+        [1e308, 0.9e308, np.finfo(np.float64).max, 2.0 ** 1022, 2.0 ** 1022, np.nextafter(2.0 ** 1023, 0)])
+    # both arguments subnormal
+    n = 5000
+    tiny = np.float64(5e-324)
+    add(rng.integers(1, 1 << 52, n) * tiny, rng.integers(1, 1 << 52, n) * tiny)
+    add(rng.integers(1, 64, 500) * tiny, rng.integers(1, 64, 500) * tiny)
+    # n/d within a few ulp of tan(pi/8), either argument the larger
+    n = 3000
+    d = 10.0 ** rng.uniform(-290, 290, n) * rng.uniform(1, 2, n)
+    nn = d * TAN_PI_8
+    for _ in range(4):
+        nn = np.where(rng.integers(0, 2, n) == 1, np.nextafter(nn, np.inf), nn)
+        nn = np.where(rng.integers(0, 2, n) == 1, np.nextafter(nn, 0), nn)
+    add(nn[: n // 2], d[: n // 2])
+    add(d[n // 2:], nn[n // 2:])
+    # ratios near 0 (down to results that underflow) and near 1
+    n = 3000
+    d = 10.0 ** rng.uniform(-150, 150, n)
+    r0 = 2.0 ** -rng.uniform(1, 1070, n)
+    add(d * r0, d)
+    add(d, d * r0)
+    n = 3000
+    d = 10.0 ** rng.uniform(-290, 290, n) * rng.uniform(1, 2, n)
+    near1 = d.copy()
+    for _ in range(6):
+        near1 = np.where(rng.integers(0, 2, n) == 1, np.nextafter(near1, 0), near1)
+    add(near1, d)
+    add(d, near1 * (1 - 10.0 ** rng.uniform(-16, -1, n)))
+    ay = np.concatenate([p[0] for p in out])
+    ax = np.concatenate([p[1] for p in out])
+    keep = (ay > 0) & (ax > 0) & np.isfinite(ay) & np.isfinite(ax)
+    return ay[keep], ax[keep]
+
+
+@pytest.fixture(scope="module")
+def atan2_cases():
+    ay, ax = _magnitude_pairs()
+    return _reference(ay, ax)
+
+
+def test_atan2_fast_within_3_ulp_of_mpmath(atan2_cases):
+    """About 2e5 argument pairs, every sign combination of each magnitude
+    pair. The worst case is printed (DESIGN.md section 2 quotes it)."""
+    y, x, ref = atan2_cases
+    assert len(y) > 190000
+    got = devtest.atan2(y, x)
+    u = _ulps(got, ref)
+    w = int(np.argmax(u))
+    print(f"atan2_fast: {len(y)} arguments, worst {float(u[w]):.0f} ulp at y={float(y[w]).hex()} "
+          f"x={float(x[w]).hex()} (got {got[w]!r}, reference {ref[w]!r}); "
+          f"{int((u > 1).sum())} above 1 ulp, {int((u > 2).sum())} above 2 ulp")
+    assert not np.isnan(got).any()
+    assert np.array_equal(np.signbit(got), np.signbit(ref))
+    assert u[w] <= ULP_BAR, (float(u[w]), float(y[w]).hex(), float(x[w]).hex())
+
+
+def test_atan2_fast_overflowing_sum_regression():
+    """n + d above DBL_MAX: the octant reduction's (n - d) / (n + d) used to
+    divide by infinity and return pi/4 for every such pair."""
+    got = devtest.atan2(np.array([0.9e308, 1e308, -0.9e308]), np.array([1e308, 0.9e308, -1e308]))
+    want = np.arctan2(np.array([0.9e308 / 4, 1e308 / 4, -0.9e308 / 4]), np.array([1e308 / 4, 0.9e308 / 4, -1e308 / 4]))
+    assert _ulps(got, want).max() <= ULP_BAR, (got, want)
+
+
+def test_atan2_fast_ieee_special_cases():
+    """+-0, +-inf, NaN and finite arguments against them, as numpy.arctan2
+    (C99 Annex F) answers: NaN where it does, the same sign everywhere (so
+    atan2(-0, x > 0) is -0), values within the same 3 ulp."""
+    big, tiny = np.finfo(np.float64).max, 5e-324
+    vals = np.array([0.0, -0.0, np.inf, -np.inf, np.nan, 1.0, -1.0, big, -big, tiny, -tiny, 2.5e-308, -3e200])
+    y, x = [a.reshape(-1) for a in np.meshgrid(vals, vals, indexing="ij")]
+    got = devtest.atan2(y, x)
+    with np.errstate(all="ignore"):
+        want = np.arctan2(y, x)
+    assert np.array_equal(np.isnan(got), np.isnan(want))
+    ok = ~np.isnan(want)
+    assert np.array_equal(np.signbit(got[ok]), np.signbit(want[ok]))
+    u = _ulps(got[ok], want[ok])
+    w = int(np.argmax(u))
+    assert u[w] <= ULP_BAR, (float(u[w]), y[ok][w], x[ok][w], got[ok][w], want[ok][w])
+    # the exact results: zeros and +-pi on the axes of zero
+    z = ok & (y == 0) & ~np.isnan(x)
+    assert np.array_equal(got[z].view(np.uint64), want[z].view(np.uint64))
+
+
+def test_cp_phase_of_all_zero_sums_is_plus_zero():
+    """cp_phase: an all-zero correlation sum (cp = 0, or silence) has phase
+    +0.0 whatever the signs of its zeros and whatever the rotation, where
+    atan2 of the rotated signed zeros would give +-pi; any other sum is
+    atan2_fast of the separately rounded complex product."""
+    zeros = np.array([complex(a, b) for a in (0.0, -0.0) for b in (0.0, -0.0)])
+    rots = np.array([1 + 0j, -1 + 0j, -1 - 1j, complex(-0.0, -1.0), 0.6 - 0.8j, complex(-0.0, -0.0)])
+    acc, rot = [a.reshape(-1) for a in np.meshgrid(zeros, rots, indexing="ij")]
+    got = devtest.cp_phase(acc, rot)
+    assert np.array_equal(got.view(np.uint64), np.zeros(len(got), np.uint64)), got
+    rng = np.random.default_rng(3)
+    acc = rng.standard_normal(512) + 1j * rng.standard_normal(512)
+    acc[:4] = [complex(0.0, 1.0), complex(-0.0, -1.0), complex(1e-320, 0.0), complex(0.0, -1e-320)]
+    rot = np.exp(1j * rng.uniform(-np.pi, np.pi, 512))
+    re = acc.real * rot.real - acc.imag * rot.imag  # each operation rounded once (no FMA), as cmul_exact
+    im = acc.real * rot.imag + acc.imag * rot.real
+    assert np.array_equal(devtest.cp_phase(acc, rot).view(np.uint64), devtest.atan2(im, re).view(np.uint64))
+
+
+# ---------------------------------------------------------------- unwrap_scan
+PI = np.float64(np.pi)
+HALF_PI = np.float64(np.pi / 2)  # M_PI / 2: its multiples up to 2 are exact
+
+
+def _lengths(nt):
+    return [1, 2, 3, nt, nt + 1, nt + 2, 2 * nt + 1, 3 * nt + 1, 4 * nt, 4 * nt + 1]
+
+
+def _wrap(v):
+    return (v + np.pi) % (2 * np.pi) - np.pi
+
+
+def _serial_stats(ph):
+    """The serial unwrap with what it did: (unwrapped, adjusted indices, number
+    of compares that tied at exactly +-pi)."""
+    out = np.array(ph, np.float64, copy=True)
+    two_pi = np.float64(2 * np.pi)
+    adj, ties = [], 0
+    for i in range(1, len(out)):
+        d = out[i] - out[i - 1]
+        ties += int(abs(d) == PI)
+        if d > PI:
+            out[i] -= two_pi
+            adj.append(i)
+        elif d < -PI:
+            out[i] += two_pi
+            adj.append(i)
+    return out, adj, ties
+
+
+def _check_bits(nt, wave, seqs):
+    got = devtest.unwrap(nt, wave, seqs)
+    for s, g in zip(seqs, got):
+        want = devtest.unwrap_serial(s)
+        bad = np.nonzero(g.view(np.uint64) != want.view(np.uint64))[0]
+        assert bad.size == 0, (f"unwrap_scan<{nt}, {wave}> n={len(s)}: {bad.size} entries differ, first at "
+                               f"{bad[0]}: got {g[bad[0]]!r}, serial {want[bad[0]]!r}")
+
+
+FORMS = pytest.mark.parametrize("nt,wave", devtest.UNWRAP_FORMS, ids=lambda v: str(v))
+
+
+@FORMS
+def test_unwrap_scan_random_sawtooth_and_pi_noise(nt, wave):
+    """Uniform phases in (-pi, pi], sawtooths of slope 0.05 .. 3.1 rad per
+    entry of either sign, and noise around +-pi: every state of the scan and
+    long runs of state changes, at every length."""
+    rng = np.random.default_rng(100 + nt + int(wave))
+    seqs = []
+    for n in _lengths(nt):
+        i = np.arange(n)
+        seqs.append(-rng.uniform(-np.pi, np.pi, n))  # (-pi, pi]
+        seqs.append(rng.uniform(-np.pi, np.pi, n))
+        for slope in (0.05, 0.7, 1.6, 2.4, 3.1):
+            for sign in (1, -1):
+                seqs.append(_wrap(sign * slope * i + rng.uniform(-np.pi, np.pi)))
+        seqs.append(rng.choice([-1.0, 1.0], n) * (np.pi - np.abs(rng.normal(0, 0.1, n))))
+        seqs.append(_wrap(np.pi + rng.normal(0, 0.05, n)))
+    # the inputs do what they are for: several adjustments per sequence on average
+    assert sum(len(_serial_stats(s)[1]) for s in seqs) > 4 * len(seqs)
+    _check_bits(nt, wave, seqs)
+
+
+@FORMS
+def test_unwrap_scan_exact_pi_ties_keep_the_entry(nt, wave):
+    """Multiples of M_PI / 2 make x - prev, x - (prev - 2 pi) and
+    x - (prev + 2 pi) equal +-M_PI exactly: the rule is a strict compare, so
+    a tie leaves the entry unadjusted, in each of the three states."""
+    rng = np.random.default_rng(200 + nt + int(wave))
+    seqs, ties = [], 0
+    for n in _lengths(nt):
+        for _ in range(4):
+            seqs.append(rng.integers(-2, 3, n) * HALF_PI)
+        seqs.append(np.where(np.arange(n) % 2 == 0, HALF_PI, -HALF_PI))   # every compare ties in state 1
+        seqs.append(np.where(np.arange(n) % 2 == 0, 0.0, PI))
+        seqs.append(np.where(np.arange(n) % 3 == 0, -PI, rng.integers(-2, 3, n) * HALF_PI))
+    for s in seqs:
+        ties += _serial_stats(s)[2]
+    assert ties > 10 * len(_lengths(nt))
+    # ties against an adjusted predecessor (states 0 and 2) occur too
+    st_ties = 0
+    for s in seqs:
+        out, adj, _ = _serial_stats(s)
+        a = set(adj)
+        st_ties += sum(1 for i in range(1, len(s)) if (i - 1) in a and abs(s[i] - out[i - 1]) == PI)
+    assert st_ties > 0
+    _check_bits(nt, wave, seqs)
+
+
+@FORMS
+def test_unwrap_scan_adjustments_only_at_thread_and_wave_boundaries(nt, wave):
+    """Flat sequences whose only adjustments sit at entries t R and t R + 1
+    for t = 63, 64, 65 (R entries per thread; t = 1 and NT - 1 as well, for
+    the forms narrower than a wave): the last entry of one thread and the
+    first of the next, across the wave boundary where NT > 64, so the state
+    must arrive through the shuffle scan and the wave totals."""
+    seqs, hits = [], 0
+    for n in _lengths(nt):
+        R = (n - 1 + nt - 1) // nt
+        for ts in ((63,), (64,), (65,), (63, 64, 65), (1,), (nt - 1,)):
+            for pair in ((0,), (1,), (0, 1)):
+                idx = sorted({t * R + o for t in ts for o in pair if 1 <= t * R + o < n})
+                for lo, hi in ((2.0, -2.5), (-2.0, 2.5)):
+                    s = np.full(n, lo)
+                    s[idx] = hi
+                    out, adj, _ = _serial_stats(s)
+                    assert adj == idx
+                    hits += len(idx)
+                    seqs.append(s)
+    assert hits > 0
+    _check_bits(nt, wave, seqs)

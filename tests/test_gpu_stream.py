@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 import oracle as O
-from common import CC, B, D, G, capture_stream, golden, impaired_stream, payload, rel_err
+from common import CC, B, D, G, STREAM_CASE, capture_stream, golden, impaired_stream, payload, rel_err, stream_case_samples
 
 pytestmark = pytest.mark.gpu
 
@@ -593,3 +593,68 @@ def test_stream_shard_margins_cover_python_sharding():
         halo, tail = modem(cfg).shard_margins()
         assert SS.stream_halo(cfg) >= halo
         assert SS.stream_tail(cfg) >= tail
+
+
+# ------------------------------------------------------------ non-flat streams
+# Streams through a multipath channel (tests/common.py STREAM_CASES; their
+# conditioning is asserted in tests/test_channel_cases.py): the detector fires
+# on the weaker early tap, so nearly every located region starts before the
+# bulk of the energy and chan_char_lq's unwrap adjusts 70 to 470 entries per
+# frame. One test per decode path, i.e. per unwrap_scan call site.
+def _check_channel_stream(name, chunk, tuning=None):
+    case = STREAM_CASE[name]
+    cfg = case[1]
+    x, x16 = stream_case_samples(case)
+    got = run_stream(cfg, x, chunk=chunk, tuning=tuning)
+    want = check_against_oracle(cfg, x, got)
+    assert len(want) >= 7
+    if x16 is not None:  # the wire format through the same path: the f64 results bit for bit
+        m = modem(cfg)
+        old = m.walk_tuning(**tuning) if tuning else None
+        try:
+            got16 = run_stream_i16(cfg, x16, chunk=chunk)
+        finally:
+            if old is not None:
+                m.walk_tuning(**old)
+        assert got16[0] == got[0]
+        for a, b in zip(got16[1:], got[1:4]):
+            assert np.array_equal(a, b)
+    return got
+
+
+@pytest.mark.parametrize("name", ["stream-D-late3", "stream-D-late7", "stream-D-three-i16"])
+def test_channel_stream_fused_decode_wave_local_unwrap(name):
+    """D geometry (N = 512, cp = 128), default tuning: stream_decode_kernel,
+    whose wave 0 runs sync_frame's wave-local unwrap_scan<64, true>. f64, and
+    int16 wire samples (stream_decode_kernel<true>) on the third stream; the
+    second has the later tap the stronger, [(0, 0.5), (7, 1.0)]."""
+    _check_channel_stream(name, 20000)
+
+
+@pytest.mark.parametrize("name", ["stream-B-late20", "stream-B-late3-i16", "stream-N1024-late20"])
+def test_channel_stream_wide_decode(name):
+    """B (N = 2048) and the N = 1024 variant, cp = N/4, default tuning:
+    stream_decode_wide_kernel<11> / <10> (ofdm_stream_wide.hip), whose
+    unwrap_scan<NT> spans NT = 256 / 128 threads, four / two wave totals.
+    f64, and int16 wire samples for B."""
+    _check_channel_stream(name, 40000)
+
+
+@pytest.mark.parametrize("name,chunk", [("stream-D-late3", 20000), ("stream-D-three-i16", 20000),
+                                        ("stream-B-late20", 40000), ("stream-B-late3-i16", 40000)])
+def test_channel_stream_staged_decode_block_unwrap(name, chunk):
+    """staged_decode = 1: pilot_freq_sinh, then stream_params_kernel<9> (D, 64
+    threads) / <11> (B, 256 threads) with the block-wide unwrap_scan<T>, then
+    the stream rx. Equal to the fused decode of the same stream: CFO and bytes
+    bit for bit, constellation 1e-9."""
+    staged = _check_channel_stream(name, chunk, tuning=dict(staged_decode=1))
+    fused = run_stream(STREAM_CASE[name][1], stream_case_samples(STREAM_CASE[name])[0], chunk=chunk)
+    assert np.array_equal(fused[1], staged[1]) and np.array_equal(fused[2], staged[2])
+    assert np.array_equal(fused[4], staged[4]) and rel_err(fused[3], staged[3]) < 1e-9
+
+
+def test_channel_stream_gathered_decode_chan_kernel():
+    """num_symb = 12 exceeds the rx register window: the located frames are
+    gathered and take the staged sync chain, whose chan_kernel<9> runs
+    unwrap_scan<64> on the gathered batch."""
+    _check_channel_stream("stream-D_s12-three", 20000)
