@@ -35,6 +35,7 @@ static constexpr int kRcclInt64 = ncclInt64, kRcclSum = ncclSum;
 #else
 static constexpr int kRcclInt64 = 4, kRcclSum = 0;  // rccl.h: ncclInt64, ncclSum (header absent at build time)
 #endif
+#include "ofdm_csi.hpp"
 #include "ofdm_internal.hpp"
 #include "ofdm_sync.hpp"
 
@@ -1138,6 +1139,34 @@ int ofdm_soft_demap(ofdm_ctx* c, const double* points, size_t n, double scale, i
     return OFDM_OK;
 }
 
+int ofdm_soft_demap_csi(ofdm_ctx* c, const double* points, size_t nframes, const double* csi, size_t csi_stride,
+                        double scale, const double* frame_scale, int fmt, void* llr_out, void* stream)
+{
+    if (!c || !points || !csi) return fail(OFDM_ERR_INVALID, "null argument");
+    if (int rc = soft_args_check(c, scale, fmt, llr_out)) return rc;
+    if (!aligned16(points)) return fail(OFDM_ERR_INVALID, "points must be 16-byte aligned");
+    if (((uintptr_t)csi & 7) || ((uintptr_t)frame_scale & 7))
+        return fail(OFDM_ERR_INVALID, "csi and frame_scale must be 8-byte aligned");
+    if (csi_stride != 0 && csi_stride < (size_t)c->D) return fail(OFDM_ERR_INVALID, "csi_stride < num_data_subc");
+    if (nframes > (size_t)LONG_MAX / ((size_t)c->D * c->S * 32)) return fail(OFDM_ERR_INVALID, "nframes out of range");
+    if (nframes == 0) return OFDM_OK;
+    ofdm::SoftCsiArgs a{};
+    a.pts = reinterpret_cast<const double2*>(points);
+    a.csi = csi;
+    a.frame_scale = frame_scale;
+    a.out = llr_out;
+    a.nframes = (long)nframes;
+    a.csi_stride = (long)csi_stride;
+    a.npts = c->D * c->S;
+    a.D = c->D;
+    a.k = c->k;
+    a.fmt = fmt;
+    a.scale = scale;
+    hipError_t e = ofdm::launch_soft_demap_csi(a, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "soft demap csi launch");
+    return OFDM_OK;
+}
+
 int ofdm_rx_demod_soft(ofdm_ctx* c, const double* iq, const int16_t* iq16, size_t nframes, size_t frame_stride,
                        const double* chan, size_t chan_stride, double scale, const double* frame_scale, int fmt,
                        void* llr_out, double* constell_out, uint8_t* bytes_out, const uint8_t* ref_bytes,
@@ -1582,6 +1611,42 @@ int ofdm_chan_estimate(ofdm_ctx* c, const double* x, size_t nframes, size_t stri
     a.pilot_ampl = (double)c->p.pilot_ampl / 1000;
     hipError_t e = ofdm::launch_chan(c->logn, a, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "chan launch");
+    return OFDM_OK;
+}
+
+int ofdm_chan_estimate_ls(ofdm_ctx* c, const double* x, size_t nframes, size_t stride, int smooth, double* chan_out,
+                          size_t chan_stride, double* csi_out, size_t csi_stride, void* stream)
+{
+    if (!c || !x) return fail(OFDM_ERR_INVALID, "null argument");
+    if (!chan_out && !csi_out) return fail(OFDM_ERR_INVALID, "chan_out and csi_out are both null");
+    if (smooth < 0 || smooth > ofdm::CSI_SMOOTH_MAX) return fail(OFDM_ERR_INVALID, "smooth outside 0..64");
+    if ((chan_out && chan_stride < (size_t)c->D) || (csi_out && csi_stride < (size_t)c->D))
+        return fail(OFDM_ERR_INVALID, "output stride < num_data_subc");
+    if (!aligned16(x) || !aligned16(chan_out)) return fail(OFDM_ERR_INVALID, "complex buffers must be 16-byte aligned");
+    if ((uintptr_t)csi_out & 7) return fail(OFDM_ERR_INVALID, "csi_out must be 8-byte aligned");
+    if (nframes > 0x7fffffffu) return fail(OFDM_ERR_INVALID, "nframes out of range");
+    if (c->P > c->N / 8) return fail(OFDM_ERR_UNSUPPORTED, "num_pilot_subc > fft_size/8");
+    if (ofdm::chan_ls_lds_bytes(c->logn, c->npr, c->D, c->P) > ofdm::CSI_LDS_MAX)
+        return fail(OFDM_ERR_UNSUPPORTED, "the preamble form's pilots and carriers do not fit the LDS");
+    if (nframes == 0) return OFDM_OK;
+    ofdm::ChanLsArgs a{};
+    a.tab = c->tables(true);
+    a.x = reinterpret_cast<const double2*>(x);
+    a.nframes = (long)nframes;
+    a.frame_stride = (long)stride;
+    a.mod_pre = c->d_modpre;
+    a.chan_out = reinterpret_cast<double2*>(chan_out);
+    a.csi_out = csi_out;
+    a.chan_stride = (long)chan_stride;
+    a.csi_stride = (long)csi_stride;
+    a.npr = c->npr;
+    a.D = c->D;
+    a.P = c->P;
+    a.cp = c->cp;
+    a.smooth = smooth;
+    a.pilot_ampl = (double)c->p.pilot_ampl / 1000;
+    hipError_t e = ofdm::launch_chan_ls(c->logn, a, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "chan_ls launch");
     return OFDM_OK;
 }
 

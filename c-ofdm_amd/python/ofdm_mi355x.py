@@ -105,6 +105,8 @@ SIGNATURES = {
     "ofdm_demap": (_I, [_V, _V, _SZ, _V, _V]),
     "ofdm_soft_demap": (_I, [_V, _V, _SZ, _D, _I, _V, _V]),
     "ofdm_rx_demod_soft": (_I, [_V, _V, _V, _SZ, _SZ, _V, _SZ, _D, _V, _I, _V, _V, _V, _V, _V, _V]),
+    "ofdm_chan_estimate_ls": (_I, [_V, _V, _SZ, _SZ, _I, _V, _SZ, _V, _SZ, _V]),
+    "ofdm_soft_demap_csi": (_I, [_V, _V, _SZ, _V, _SZ, _D, _V, _I, _V, _V]),
     "ofdm_fec_coded_bits": (_I, [_SZ, _I, C.POINTER(_SZ)]),
     "ofdm_fec_max_info_bits": (_I, [_SZ, _I, C.POINTER(_SZ)]),
     "ofdm_fec_workspace_size": (_I, [_SZ, _SZ, C.POINTER(_SZ)]),
@@ -348,6 +350,26 @@ class Modem:
                                        _ptr(chan), chan_stride, scale, _ptr(frame_scale), fmt, _ptr(llr_out),
                                        _ptr(constell_out), _ptr(bytes_out), _ptr(ref), _ptr(bit_errors),
                                        _stream(stream)))
+
+    # ---- frequency-selective channels
+    def chan_estimate_ls(self, x, nframes: int, frame_stride: int, chan_out=None, csi_out=None, smooth: int = 0,
+                         chan_stride: int | None = None, csi_stride: int | None = None, stream=None):
+        """ofdm_chan_estimate_ls: the per-carrier least-squares estimate H
+        (complex128 chan_out) and |H|^2 (float64 csi_out) of each frame's
+        preamble form; strides in elements, num_data_subc by default."""
+        d = self.params.num_data_subc
+        check(lib().ofdm_chan_estimate_ls(self.h, _ptr(x), nframes, frame_stride, smooth, _ptr(chan_out),
+                                          d if chan_stride is None else chan_stride, _ptr(csi_out),
+                                          d if csi_stride is None else csi_stride, _stream(stream)))
+
+    def soft_demap_csi(self, points, nframes: int, csi, llr_out, scale: float = 1.0, fmt: int = LLR_F32,
+                       frame_scale=None, csi_stride: int | None = None, stream=None):
+        """ofdm_soft_demap_csi: nframes * num_data_subc * num_symb points ->
+        LLRs scaled by scale * frame_scale[f] * csi[f*csi_stride + carrier];
+        csi_stride in doubles (num_data_subc by default, 0: one shared vector)."""
+        cs = self.params.num_data_subc if csi_stride is None else csi_stride
+        check(lib().ofdm_soft_demap_csi(self.h, _ptr(points), nframes, _ptr(csi), cs, scale, _ptr(frame_scale), fmt,
+                                        _ptr(llr_out), _stream(stream)))
 
     # ---- channel code (K=7 133/171, soft-input Viterbi)
     fec_coded_bits = staticmethod(fec_coded_bits)

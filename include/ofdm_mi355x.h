@@ -20,7 +20,8 @@
  *     rx_demod and its _i16 / _read / _soft forms, map, demap, soft_demap,
  *     fec_encode, fec_decode, interleave_bits, interleave_llr, scramble, fft_write, fft_read, bit_convert,
  *     int16_to_double, double_to_int16, t2_scan, find_preamble, cfo_estimate,
- *     freq_shift, cp_sync, phase_sync, sync_chain, chan_estimate, sync_frames)
+ *     freq_shift, cp_sync, phase_sync, sync_chain, chan_estimate, sync_frames,
+ *     chan_estimate_ls, soft_demap_csi)
  *     and ofdm_copy only launch kernels on `stream`: no
  *     allocation, no host copy, no synchronisation, and every per-launch
  *     device counter is left as the next launch needs it. A chain of them can
@@ -292,6 +293,73 @@ int ofdm_rx_demod_soft(ofdm_ctx* ctx, const double* iq, const int16_t* iq16,
                        const uint8_t* ref_bytes, unsigned long long* bit_errors,
                        void* stream);
 
+/* ---- frequency-selective channels: a per-carrier least-squares channel
+ * estimate from the preamble, and LLRs weighted by the channel state. The
+ * receive chain (INTEGRATION.md "Frequency-selective channels"):
+ *     ofdm_sync_frames, ofdm_chan_estimate_ls on the synced preamble,
+ *     ofdm_rx_demod(chan = H, constell_out), ofdm_soft_demap_csi,
+ *     ofdm_interleave_llr, ofdm_fec_decode, ofdm_scramble.
+ *
+ * ofdm_chan_estimate_ls. x, nframes and frame_stride are ofdm_chan_estimate's
+ * (below): frame f's preamble form, num_pr_symb [CP|body] symbols, starts at
+ * x + 2*f*frame_stride and is not modified. With D = num_data_subc:
+ *   input points   pr[s*D + c] = FFT_FORM::read of the preamble form
+ *                  (Frame.cpp:73-96 on its num_pr_symb symbols: phys over the
+ *                  form's own pilots, the per-segment coef against symbol 0),
+ *                  the points ofdm_chan_estimate starts from;
+ *   preamble points m = mod_preamble (ofdm_get_preamble), D per symbol;
+ *   raw estimate   raw[c] = (1/num_pr_symb) * sum_s pr[s*D+c] / m[s*D+c],
+ *                  s ascending;
+ *   smoothing      half-width w = smooth, 0 <= w <= 64: H[c] = the mean of
+ *                  raw[a..b], summed in ascending order and divided by the
+ *                  count, a = max(lo, c-w), b = min(hi-1, c+w), where
+ *                  [lo, hi) is the half of the data carriers that holds c,
+ *                  [0, D/2) or [D/2, D): the two sides of DC in the carrier
+ *                  order, the split chan_char_lq makes. w = 0: H = raw.
+ *   outputs        chan_out[f*chan_stride + c] = H[c] (complex: a drop-in for
+ *                  the `chan` of ofdm_rx_demod*), csi_out[f*csi_stride + c] =
+ *                  re(H)^2 + im(H)^2 (one double). Either may be NULL, not
+ *                  both; strides in elements, >= D for each output given.
+ * The kernel applies 1/phys and 1/num_pr_symb after the sum (phys is known
+ * after the last symbol): equal to the definition within 1e-9 * max|H|.
+ * Every geometry ofdm_chan_estimate accepts, num_data_subc > fft_size/2
+ * included. Asynchronous: no allocation, no host copy, no synchronisation;
+ * capturable. OFDM_ERR_INVALID: null x, both outputs null, smooth out of
+ * range, a stride below D, misaligned buffers (complex 16, csi_out 8 bytes).
+ * OFDM_ERR_UNSUPPORTED, before anything is launched: a geometry whose LDS
+ * need (fft_size + fft_size/64 + 80 + num_pr_symb*num_pilot_subc + D complex
+ * values) exceeds 160 KB. nframes == 0: OFDM_OK, no launch.
+ *
+ * ofdm_soft_demap_csi. points: nframes * D * num_symb equalised points in
+ * constell_out order (device, 16-byte aligned, not modified); point i of
+ * frame f sits on carrier c = i mod D. csi: D doubles per frame at
+ * csi + f*csi_stride (csi_stride = 0: one vector shared by every frame).
+ * frame_scale: nullable, as ofdm_rx_demod_soft's.
+ *   llr[(f*D*num_symb + i)*k + b] = s * (d1 - d0),
+ *   s = scale * frame_scale[f] * csi[f*csi_stride + c],
+ * d0, d1 the max-log minima of "soft decisions" above. Formats, rounding,
+ * saturation and alignment rules are ofdm_soft_demap's.
+ * Erasures: a point with a non-finite component, or a weight csi[..] that is
+ * not finite and > 0 (zero, negative, inf, NaN), gives exactly 0 for all k
+ * LLRs of the point (+0.0 in OFDM_LLR_F32): an H[c] = 0 division in the rx
+ * does not send NaN into the decoder.
+ * OFDM_ERR_INVALID: null points, csi or llr_out, unknown fmt, scale not
+ * finite or <= 0, misaligned buffers, 0 < csi_stride < D.
+ * OFDM_ERR_UNSUPPORTED: k outside 1, 2, 4, 6, 8. nframes == 0: OFDM_OK.
+ * Asynchronous; capturable.
+ * The Viterbi decoder is invariant to a common scale of a codeword's LLRs:
+ * only the relative weights of the carriers matter.
+ * Not covered: the weight fused into ofdm_rx_demod_soft (the rx kernels are
+ * untouched), the stream decodes and the compat layer, a noise-variance
+ * estimate, MMSE equalisation, interpolation from the pilots alone. */
+int ofdm_chan_estimate_ls(ofdm_ctx* ctx, const double* x, size_t nframes, size_t frame_stride,
+                          int smooth, double* chan_out, size_t chan_stride,
+                          double* csi_out, size_t csi_stride, void* stream);
+int ofdm_soft_demap_csi(ofdm_ctx* ctx, const double* points, size_t nframes,
+                        const double* csi, size_t csi_stride,
+                        double scale, const double* frame_scale,
+                        int fmt, void* llr_out, void* stream);
+
 /* ---- channel code: the rate-1/2, constraint-length-7 convolutional code
  * (generators 133/171 octal, 802.11 / DVB) with its 2/3 and 3/4 puncturings,
  * and a soft-input Viterbi decoder fed by the LLRs above. Definition:
@@ -402,7 +470,8 @@ int ofdm_fec_decode(ofdm_ctx* ctx, const void* llr, int fmt, size_t llr_stride, 
  * out with other than equal strides). nblocks == 0 or ncw == 0: OFDM_OK, no
  * launch. A grid that does not fit: OFDM_ERR_HIP, nothing launched.
  * Not covered: the deinterleave fused into the decoder or the soft rx, a CRC,
- * per-carrier weighting of the LLRs, and the compat layer. */
+ * the per-carrier weight of ofdm_soft_demap_csi fused into ofdm_rx_demod_soft,
+ * a noise-variance estimate, MMSE equalisation, and the compat layer. */
 enum { OFDM_IL_FORWARD = 0, OFDM_IL_INVERSE = 1 };
 
 /* Host arithmetic: the context's per-symbol block, num_data_subc*modType
