@@ -137,6 +137,11 @@ struct ofdm_ctx {
     int* d_tx_code = nullptr;
     double2* d_const = nullptr;
     double2* d_const_bpsk = nullptr;
+    // decide_select's thresholds (the rx emit's fast path, k = 2), found on
+    // the device at creation; dec_fast = false: the scan's checks failed or
+    // k is not 2, and rx keeps the decision arithmetic
+    double dec_tau[3] = {};
+    bool dec_fast = false;
     double2* d_header = nullptr;   // T2 + preamble
     double2* d_preamble = nullptr; // ofdm_preamble (preamble_len)
     double2* d_templ = nullptr;    // pr_sin_len
@@ -486,6 +491,21 @@ int ofdm_create(const ofdm_params* params, int device, ofdm_ctx** out)
         return rc;
     }
 
+    if (c->k == 2) {  // the rx emit's fast path takes QPSK only (16-QAM measured no gain)
+        double* d_tau = nullptr;
+        double h_tau[4] = {};
+        hipError_t e = hipMalloc((void**)&d_tau, sizeof(h_tau));
+        if (e == hipSuccess) e = ofdm::launch_decide_tau_scan(c->k, d_tau, nullptr);
+        if (e == hipSuccess) e = hipMemcpy(h_tau, d_tau, sizeof(h_tau), hipMemcpyDeviceToHost);
+        if (d_tau) (void)hipFree(d_tau);
+        if (e != hipSuccess) {
+            ofdm_destroy(c);
+            return hip_fail(e, "decision threshold scan");
+        }
+        for (int j = 0; j < 3; ++j) c->dec_tau[j] = h_tau[j];
+        c->dec_fast = h_tau[3] == 1.0;
+    }
+
     // T2SIN_FORM::set (Frame.cpp:139-154): X[f1] = X[f2] = 0.5, unnormalised
     // backward DFT of T2sin_size points = two complex tones of amplitude 0.5.
     c->t2_symbol.assign(c->t2, cd(0, 0));
@@ -757,6 +777,8 @@ int ofdm_get_geometry(const ofdm_ctx* c, ofdm_geometry* o)
     return OFDM_OK;
 }
 
+int ofdm_rx_emit_fast(const ofdm_ctx* c) { return c ? (c->dec_fast ? 1 : 0) : -1; }
+
 int ofdm_get_t2_symbol(const ofdm_ctx* c, double* o)
 {
     if (!c || !o) return fail(OFDM_ERR_INVALID, "null argument");
@@ -1011,6 +1033,8 @@ static int rx_demod_impl(ofdm_ctx* c, const double* iq, const int16_t* iq16, siz
     a.bytes_per_frame = c->geo.bytes_per_frame;
     a.pilot_ampl = (double)c->p.pilot_ampl / 1000;
     a.queue = rx_queue(c, (hipStream_t)stream);
+    for (int j = 0; j < 3; ++j) a.dec_tau[j] = c->dec_tau[j];
+    a.dec_fast = c->dec_fast;
     const bool fits = c->S <= ofdm::RX_SMAX && c->D <= ofdm::RX_DPT * (c->N / 8);
     if (!fits) {
         if (c->D > ofdm::RX_DPT * (c->N / 8))

@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <mutex>
 #include <set>
+#include <type_traits>
 #include <utility>
 
 #include "ofdm_fft.hpp"
@@ -42,6 +43,167 @@ __device__ __forceinline__ int decide_select(double2 z, int k, double s1, int m)
     const int qam = (ire | (iim * m)) & 0xff;
     const int bpsk = (z.x + z.y) > 0.0;
     return k == 1 ? bpsk : qam;
+}
+
+// ---- the QAM decision as threshold compares (the rx emit's fast path).
+// decide_select's per-axis level is a composition of monotone steps (clamp,
+// rounded add, rounded multiply by s1 > 0, rounded add, truncation), so it is
+// a monotone step function of the coordinate: the level equals the number of
+// thresholds tau_1 < tau_2 < ... the coordinate has reached. The tau are
+// particular doubles, not the nominal cell edges (QPSK: tau_1 is just below 0,
+// because x + 1 rounds to 1 there); decide_tau_scan finds them by evaluating
+// decide_select itself. A NaN reaches no threshold: level 0, as decide_select.
+// The product runs K = 2 only: the K = 4 forms of axis_tau, emit_collects and
+// emit_words below are the record of the 16-QAM emit that measured no gain
+// (DESIGN section 4), reached through the devtest library and tested there,
+// so that the experiment can be repeated without rewriting them.
+constexpr int DEC_TAU_MAX = 3;  // m - 1 thresholds per axis, m <= 4 (k = 2, 4)
+
+// Level of one axis for k in {2, 4}: the bits come from the nested compare
+// masks (16-QAM: high bit [x >= tau_2], low bit the parity of the three).
+template <int K>
+__device__ __forceinline__ unsigned axis_tau(double x, const double (&tau)[DEC_TAU_MAX])
+{
+    static_assert(K == 2 || K == 4, "thresholds cover QPSK and 16-QAM");
+    if constexpr (K == 2) {
+        return x >= tau[0] ? 1u : 0u;
+    } else {
+        const bool c0 = x >= tau[0], c1 = x >= tau[1], c2 = x >= tau[2];
+        return (c1 ? 2u : 0u) | ((c0 != c1) != c2 ? 1u : 0u);
+    }
+}
+
+// decide_select(z, K, ...) from thresholds: re | im * m, K bits.
+template <int K>
+__device__ __forceinline__ unsigned decide_tau(double2 z, const double (&tau)[DEC_TAU_MAX])
+{
+    return axis_tau<K>(z.x, tau) | (axis_tau<K>(z.y, tau) << (K / 2));
+}
+
+// Order-preserving map between doubles and signed 64-bit keys (-0 < +0,
+// adjacent doubles are adjacent keys), NaNs excluded.
+__device__ __forceinline__ long long dbl_key(double x)
+{
+    const long long b = __double_as_longlong(x);
+    return b ^ ((b >> 63) & 0x7fffffffffffffffLL);
+}
+__device__ __forceinline__ double key_dbl(long long k)
+{
+    return __longlong_as_double(k ^ ((k >> 63) & 0x7fffffffffffffffLL));
+}
+
+// The thresholds of k in {2, 4}, found on the device from decide_select
+// itself. One workgroup of 256 threads; out[0 .. DEC_TAU_MAX-1] = tau (unused
+// entries +inf), out[DEC_TAU_MAX] = 1.0 if every check below held, else 0.0
+// (the context then does not offer the fast path):
+//   * thread 0 bisects, in key order, for the smallest double whose level is
+//     >= j between nominal edge -+ 1/4 (levels j-1 and j there);
+//   * every thread then compares decide_select with the threshold count on
+//     the 2048 doubles around each tau (monotone across the step), on 4096
+//     points of a sweep over [-1.5, 1.5], and on the special values
+//     (+-0, +-1 and neighbours, +-2, +-inf, NaN), both axes.
+// lds: DEC_TAU_MAX + 1 doubles.
+__device__ __forceinline__ void decide_tau_scan(int k, double* __restrict__ out, double* lds)
+{
+    const int m = 1 << (k / 2);
+    const double s1 = 1.0 / (2.0 / (m - 1));  // rx_kernel's expression
+    auto level = [&](double x) { return decide_select(make_double2(x, -1.0), k, s1, m) & (m - 1); };
+    const int t = threadIdx.x;
+    if (t == 0) {
+        bool ok = true;
+        for (int j = 1; j < DEC_TAU_MAX + 1; ++j) {
+            if (j >= m) {
+                lds[j - 1] = __longlong_as_double(0x7ff0000000000000LL);
+                continue;
+            }
+            const double edge = -1.0 + (double)(2 * j - 1) / (double)(m - 1);
+            long long lo = dbl_key(edge - 0.25), hi = dbl_key(edge + 0.25);
+            ok = ok && level(key_dbl(lo)) == j - 1 && level(key_dbl(hi)) == j;
+            while (hi - lo > 1) {  // level(lo) < j <= level(hi)
+                const long long mid = lo + (hi - lo) / 2;
+                if (level(key_dbl(mid)) >= j)
+                    hi = mid;
+                else
+                    lo = mid;
+            }
+            lds[j - 1] = key_dbl(hi);
+        }
+        lds[DEC_TAU_MAX] = ok ? 1.0 : 0.0;
+    }
+    __syncthreads();
+    double tau[DEC_TAU_MAX];
+    for (int j = 0; j < DEC_TAU_MAX; ++j) tau[j] = lds[j];
+    bool ok = lds[DEC_TAU_MAX] != 0.0;
+    auto same = [&](double x, double y) {
+        const double2 z = make_double2(x, y);
+        const unsigned want = (unsigned)decide_select(z, k, s1, m);
+        return want == (k == 2 ? decide_tau<2>(z, tau) : decide_tau<4>(z, tau));
+    };
+    for (int j = 0; j < m - 1; ++j) {
+        const long long c = dbl_key(tau[j]);
+        int prev = level(key_dbl(c - 1024 + t * 8 - 1));
+        for (int e = 0; e < 8; ++e) {
+            const double x = key_dbl(c - 1024 + t * 8 + e);
+            const int lv = level(x);
+            ok = ok && lv >= prev && same(x, -x) && same(-x, x);
+            prev = lv;
+        }
+    }
+    for (int i = t; i < 4096; i += 256) {
+        const double x = -1.5 + 3.0 * (double)i / 4095.0;
+        ok = ok && same(x, 0.3 - x) && level(x) <= level(x + 3.0 / 4095.0);
+    }
+    const double inf = __longlong_as_double(0x7ff0000000000000LL), qnan = __longlong_as_double(0x7ff8000000000000LL);
+    const double sp[16] = {0.0, -0.0, 1.0, -1.0, 1.0 + DBL_EPSILON, 1.0 - DBL_EPSILON / 2, -1.0 - DBL_EPSILON,
+                           -1.0 + DBL_EPSILON / 2, 2.0, -2.0, inf, -inf, qnan, -qnan, 0.5, -0.5};
+    ok = ok && same(sp[t & 15], sp[(t >> 4) & 15]);
+    const int all = __syncthreads_and(ok ? 1 : 0);
+    if (t == 0) {
+        for (int j = 0; j < DEC_TAU_MAX; ++j) out[j] = tau[j];
+        out[DEC_TAU_MAX] = all ? 1.0 : 0.0;
+    }
+}
+
+// One symbol's output words, assembled inside a wave (whole waves, uniform
+// control flow). Lane l holds in `bits` its K-bit decisions of the symbol's
+// four 64-carrier groups (carriers w0 + T*g + l), group g in byte g. An output
+// byte takes LPB = 8/K consecutive carriers, MSB first (pack_word's order):
+// each lane shifts its decisions to their place in the byte and the LPB lanes
+// of a byte are OR-ed by quad permutations, which leaves in each of them
+// v: byte g = output byte l/LPB of group g. Four consecutive bytes of one
+// group (an output word) then sit in byte g of four neighbouring lane cells
+// of one 16-lane row: each lane moves the byte of "its" group(s) to the
+// byte's place in the word, and the last cell of the four (the collecting
+// lanes, emit_collects) ORs the cells below it in by row shifts.
+//   K = 2: w[0] = word l/16 of group l & 3                  (lanes 12..15 of a row)
+//   K = 4: w[h] = word l/8 of group (l & 1) + 2h, h = 0, 1  (lanes 6, 7, 14, 15)
+// Values in the other lanes are partial.
+template <int K>
+__device__ __forceinline__ bool emit_collects(int lane)
+{
+    return ((lane / (8 / K)) & 3) == 3;
+}
+
+template <int K>
+__device__ __forceinline__ void emit_words(unsigned bits, int lane, unsigned (&w)[K / 2])
+{
+    constexpr int LPB = 8 / K;
+    auto dpp = [](unsigned x, auto ctrl) {  // lanes without a source read 0
+        return (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, decltype(ctrl)::value, 0xf, 0xf, true);
+    };
+    const int r = lane & (LPB - 1);
+    unsigned v = bits << (K * (LPB - 1 - r));
+    v |= dpp(v, std::integral_constant<int, 0xB1>{});  // quad_perm [1,0,3,2]
+    if constexpr (LPB == 4) v |= dpp(v, std::integral_constant<int, 0x4E>{});  // quad_perm [2,3,0,1]
+    const int q = (lane / LPB) & 3;  // this cell's byte within its output words
+#pragma unroll
+    for (int h = 0; h < K / 2; ++h) {
+        const int g = r + LPB * h;
+        const unsigned b = ((v >> (8 * g)) & 0xffu) << (8 * q);
+        w[h] = b | dpp(b, std::integral_constant<int, 0x110 + LPB>{})       // row_shr: lane i reads lane i - n
+                 | dpp(b, std::integral_constant<int, 0x110 + 2 * LPB>{})
+                 | dpp(b, std::integral_constant<int, 0x110 + 3 * LPB>{});
+    }
 }
 
 // ---- soft decisions: max-log LLRs of the reference's constellation

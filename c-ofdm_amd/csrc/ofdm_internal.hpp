@@ -76,6 +76,11 @@ struct RxArgs {
     int S, D, P, seg, cp, k;
     long bytes_per_frame;
     double pilot_ampl;
+    // the emit's fast path (hard decisions of k = 2 as threshold compares,
+    // output words assembled in the wave): the context's thresholds of
+    // decide_select (ofdm_dev.hpp decide_tau_scan); dec_fast = 0: not offered
+    double dec_tau[3];
+    int dec_fast;
 };
 
 // The soft rx's own arguments (rx_soft_kernel's second parameter: RxArgs and
@@ -92,6 +97,8 @@ hipError_t launch_rx_soft(int logn, const RxArgs& a, const SoftArgs& sa, hipStre
 hipError_t launch_soft_demap(const double2* pts, long n, int k, double scale, int fmt, void* out, hipStream_t stream);
 hipError_t launch_tx(int logn, const TxArgs& a, hipStream_t stream);
 hipError_t launch_rx(int logn, const RxArgs& a, hipStream_t stream, bool* staged_needed);
+// decide_tau_scan for k in {2, 4}: out = 3 thresholds + the checks' verdict (4 doubles, device)
+hipError_t launch_decide_tau_scan(int k, double* out, hipStream_t stream);
 hipError_t launch_copy(void* dst, const void* src, size_t n, hipStream_t stream);  // kernel copy (device / mapped pinned)
 hipError_t launch_demap(double2* pts, long n, int k, uint8_t* bytes, hipStream_t stream);
 hipError_t launch_map(const uint8_t* bytes, long nbytes, int k, const double2* table, double2* out,

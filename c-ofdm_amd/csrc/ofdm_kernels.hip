@@ -1003,6 +1003,20 @@ hipError_t launch_rx(int logn, const RxArgs& a, hipStream_t st, bool* staged)
     }
 }
 
+// The thresholds of the emit's fast path (ofdm_dev.hpp), once per context.
+__global__ void __launch_bounds__(256) decide_tau_scan_kernel(int k, double* out)
+{
+    __shared__ double lds[DEC_TAU_MAX + 1];
+    decide_tau_scan(k, out, lds);
+}
+
+hipError_t launch_decide_tau_scan(int k, double* out, hipStream_t st)
+{
+    if (k != 2 && k != 4) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(decide_tau_scan_kernel, dim3(1), dim3(256), 0, st, k, out);
+    return hipGetLastError();
+}
+
 hipError_t launch_demap(double2* pts, long n, int k, uint8_t* bytes, hipStream_t st)
 {
     const long nbytes = (n * k + 7) / 8;

@@ -76,6 +76,7 @@
 #pragma unroll 1
     for (long fnext; fl < nfr; fl = fnext) {
         const long f = frame_of(fl);
+        OFDM_PHASE(rx_symbols);
         // Opaque per-frame copies of the thread index, the carrier tables and
         // the geometry: everything derived from them is recomputed per frame
         // instead of being hoisted out of the frame loop and held live beside
@@ -180,6 +181,7 @@
             }
         }
         lds_barrier();  // pilots of the last symbol visible; every thread is done reading bufB
+        OFDM_PHASE(rx_phys_gains);
         // The channel carriers go to LDS (bufA past the decisions) by DMA
         // issued ahead of the next frame's symbol 0: read per point from HBM
         // behind that DMA (in-order returns), they cost the stream rx ~18%.
@@ -188,6 +190,26 @@
         double2* chl = reinterpret_cast<double2*>(reinterpret_cast<char*>(bufA) + dec_b);
         const bool chan_lds = chan && dec_b + D * 16 <= N * 16;  // uniform
         if (chan_lds) dma_chan<LOGN>(chan, D, chl, t);
+        // The emit's fast path (below): hard decisions of k = 2 without a
+        // channel, every 64-carrier group of a wave (d = w0 + T*g + lane)
+        // wholly inside or outside D, word-aligned outputs. Uniform.
+        // (emit_fast and its helpers are written for k = 4 as well; at 16-QAM
+        // they measured no gain over the LDS path, DESIGN section 4, so k = 4
+        // stays there and the kernel instantiates K = 2 only.)
+        bool fast = false;
+        if constexpr (!SOFT && !STAGED && !SYNC && T >= 64)
+            fast = a.dec_fast && !chan && a.k == 2 && (D & 63) == 0 && by_word &&
+                   ((uintptr_t)a.ref & 15) == 0;
+        // Its reference bytes go to LDS (bufA: free since the pilot barrier,
+        // and this path keeps no decisions there) by the channel's DMA, ahead
+        // of the emit's first store and behind the gains: vmcnt counts stores
+        // too, so a load issued after the frame's stores would wait for all
+        // of them. bpf is a multiple of 16 here and bpf / 16 <= T.
+        uint8_t* refl = reinterpret_cast<uint8_t*>(bufA);
+        const bool ref_lds = fast && a.ref;  // uniform
+        if (ref_lds)
+            dma_chan<LOGN>(reinterpret_cast<const double2*>(a.ref + f * bpf), (int)(bpf >> 4),
+                           reinterpret_cast<double2*>(refl), t);
         // Static frame order (no queue; the stream decode): the next frame's
         // symbol 0 streams into bufB (free since the pilot barrier) from here,
         // behind the channel carriers, so it overlaps the gains as well.
@@ -217,7 +239,7 @@
             const double2 g = cdiv_exact(make_double2(1.0, 0.0), coef);
             gain[i] = make_double2(g.x / phys, g.y / phys);
         }
-        if (chan_lds) {  // the channel DMA landed (the 8 symbol-0 transfers issued after it may still fly)
+        if (chan_lds || ref_lds) {  // that DMA landed (the 8 symbol-0 transfers issued after it may still fly)
             if (early && fnext < nfr)
                 asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
             else
@@ -281,6 +303,57 @@
             }
         };
 
+        // The fast path's symbol: the unchanged cmul_exact and constellation
+        // store per point, the decision as threshold compares (decide_tau),
+        // and the symbol's output words assembled in the wave (emit_words):
+        // no decision goes through LDS and no packing pass follows. The
+        // active groups (g < na, uniform) are straight-line code and their
+        // gain reads are issued together; the collecting lanes store the
+        // words and count the bit errors against the reference in LDS.
+        auto emit_fast = [&](int s, const double2 (&yw)[RX_DPT], auto kc) {
+            constexpr int K = decltype(kc)::value, LPB = 8 / K;
+            const double tau[DEC_TAU_MAX] = {a.dec_tau[0], a.dec_tau[1], a.dec_tau[2]};
+            // opaque copy of the thread index: everything derived from it is
+            // computed per symbol, not hoisted out of the emit loop and held
+            // (eight symbols' worth) beside the register window
+            int tt;
+            asm volatile("v_mov_b32 %0, %1" : "=v"(tt) : "v"(t));
+            const int lane = tt & 63;
+            const int w0 = __builtin_amdgcn_readfirstlane(tt & ~63);
+            const int na = w0 < D ? min((D - w0 + T - 1) / T, RX_DPT) : 0;  // uniform: this wave's groups inside D
+            double2* cbase = a.constell + (f * S + s) * D;
+            double2 gv[RX_DPT];
+#pragma unroll
+            for (int i = 0; i < RX_DPT; ++i) {
+                int gi = s * P + (pk[i] >> 16);
+                asm volatile("" : "+v"(gi));
+                gv[i] = gain[gi];
+            }
+            unsigned bits = 0;
+#pragma unroll
+            for (int i = 0; i < RX_DPT; ++i) {
+                const double2 o = cmul_exact(yw[i], gv[i]);
+                int d = tt + T * i;
+                asm volatile("" : "+v"(d));
+                if (a.constell && i < na) store_nt(cbase + d, o);
+                bits |= decide_tau<K>(o, tau) << (8 * i);
+            }
+            unsigned w[K / 2];
+            emit_words<K>(bits, lane, w);
+            if (emit_collects<K>(lane)) {
+#pragma unroll
+                for (int h = 0; h < K / 2; ++h) {
+                    const int g = (lane & (LPB - 1)) + LPB * h;
+                    if (g < na) {
+                        // byte offset of this lane's word within the frame
+                        const int off = (((s * D + w0 + T * g) * K) >> 3) + 4 * (lane / (4 * LPB));
+                        if (a.bytes) *reinterpret_cast<uint32_t*>(a.bytes + f * bpf + off) = w[h];
+                        if (a.ref) errs += __popc(w[h] ^ *reinterpret_cast<const uint32_t*>(refl + off));
+                    }
+                }
+            }
+        };
+
         auto pack = [&](long jb0, long jb1, long dbase) {
             for (long jb = jb0 + t; jb < jb1; jb += T) {
                 int byte = 0;
@@ -317,7 +390,33 @@
             }
         };
 
-        if constexpr (!STAGED) {
+        if (fast) {  // only ever true where the constexpr below holds
+            if constexpr (!SOFT && !STAGED && !SYNC && T >= 64) {
+                OFDM_PHASE(rx_emit_fast);
+#pragma unroll 1
+                for (int w = 0; w < S; ++w) {
+                    switch (w) {
+#define OFDM_RX_FAST(W)                                           \
+    case W:                                                       \
+        if constexpr (W < SW) {                                   \
+            emit_fast(w, y[W], std::integral_constant<int, 2>{}); \
+        }                                                         \
+        break;
+                        OFDM_RX_FAST(0) OFDM_RX_FAST(1) OFDM_RX_FAST(2) OFDM_RX_FAST(3)
+                        OFDM_RX_FAST(4) OFDM_RX_FAST(5) OFDM_RX_FAST(6) OFDM_RX_FAST(7)
+#undef OFDM_RX_FAST
+                        default: break;
+                    }
+                }
+                // No barrier and no packing pass here: the decisions never
+                // went to LDS (`dec`, the alias of the FFT image, is not
+                // written on this path), so the barrier that ordered the dec
+                // writes before pack_words' reads has nothing to order. pil,
+                // gain, red and the queue slot are still ordered by the
+                // frame's last barrier below.
+            }
+        } else if constexpr (!STAGED) {
+            OFDM_PHASE(rx_emit);
             // one symbol per (non-unrolled) iteration: a case's register
             // indices are compile-time, and the scheduler cannot interleave
             // symbols (the next frame's symbol 0 is live in registers here)
@@ -357,11 +456,13 @@
                 }
             }
             lds_barrier();
+            OFDM_PHASE(rx_pack);
             if (by_word)
                 pack_words();
             else
                 pack(0, bpf, 0);
         } else {
+            OFDM_PHASE(rx_emit);
             const long bps = (long)D * a.k / 8;  // bytes per symbol (host checks D*k % 8 == 0)
             for (int s = 0; s < S; ++s) {
                 double2 yst[RX_DPT];
@@ -377,8 +478,10 @@
             }
             if (whole_frame_dec) pack(0, bpf, 0);
         }
-        lds_barrier();  // dec / pil / gain / red are rewritten by the next frame
+        OFDM_PHASE(rx_frame_end);
+        lds_barrier();  // dec (or the fast path's reference bytes) / pil / gain / red are rewritten by the next frame
     }
+    OFDM_PHASE(rx_end);
     if (a.bit_errors) {
         errs = block_sum_u64<T>(errs, red);
         if (t0 == 0 && errs) atomicAdd(a.bit_errors, errs);

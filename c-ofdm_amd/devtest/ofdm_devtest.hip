@@ -1,11 +1,14 @@
-// ofdm_devtest.hip — test-only launchers for two device primitives of the rx
-// sync front end that no C-ABI entry reaches with chosen arguments:
-// atan2_fast / cp_phase (ofdm_fft.hpp) and unwrap_scan (ofdm_syncdev.hpp).
+// ofdm_devtest.hip — test-only launchers for device primitives that no C-ABI
+// entry reaches with chosen arguments: atan2_fast / cp_phase (ofdm_fft.hpp),
+// unwrap_scan (ofdm_syncdev.hpp), and the rx emit's fast path (ofdm_dev.hpp):
+// the threshold scan, the decision by thresholds beside decide_select, and
+// the in-wave assembly of output words.
 // Built into lib/libofdm_devtest.so, a library of its own: nothing here is
 // linked into libofdm_mi355x.so. Every launcher takes device pointers and a
 // stream, launches one kernel and returns the launch's hipError_t.
 #include <hip/hip_runtime.h>
 
+#include "../csrc/ofdm_dev.hpp"
 #include "../csrc/ofdm_syncdev.hpp"
 
 namespace {
@@ -51,9 +54,74 @@ int launch_unwrap(double* ph, const int* len, int nseq, long stride, hipStream_t
     return (int)hipGetLastError();
 }
 
+__global__ void __launch_bounds__(256) tau_scan_kernel(int k, double* out)
+{
+    __shared__ double lds[ofdm::DEC_TAU_MAX + 1];
+    ofdm::decide_tau_scan(k, out, lds);
+}
+
+// z: n points; sel[i] = decide_select, thr[i] = decide_tau<K> with tau[0..2]
+template <int K>
+__global__ void decide_kernel(const double2* __restrict__ z, const double* __restrict__ tau,
+                              uint8_t* __restrict__ sel, uint8_t* __restrict__ thr, long n)
+{
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int m = 1 << (K / 2);
+    const double s1 = 1.0 / (2.0 / (m - 1));  // rx_kernel's expression
+    const double t[ofdm::DEC_TAU_MAX] = {tau[0], tau[1], tau[2]};
+    sel[i] = (uint8_t)ofdm::decide_select(z[i], K, s1, m);
+    thr[i] = (uint8_t)ofdm::decide_tau<K>(z[i], t);
+}
+
+// One wave per workgroup: bits[64 b + lane] in, emit_words' K/2 words of every
+// lane out (words[(64 b + lane) * 2 + h]; h = 1 unused for K = 2).
+template <int K>
+__global__ void __launch_bounds__(64) emit_words_kernel(const unsigned* __restrict__ bits,
+                                                        unsigned* __restrict__ words)
+{
+    const long i = (long)blockIdx.x * 64 + threadIdx.x;
+    unsigned w[K / 2];
+    ofdm::emit_words<K>(bits[i], (int)threadIdx.x, w);
+    for (int h = 0; h < K / 2; ++h) words[2 * i + h] = w[h];
+}
+
 }  // namespace
 
 extern "C" {
+
+// the context's threshold scan: out = 3 thresholds + verdict (4 doubles)
+int ofdm_devtest_tau_scan(int k, double* out, hipStream_t s)
+{
+    if (k != 2 && k != 4) return -1;
+    hipLaunchKernelGGL(tau_scan_kernel, dim3(1), dim3(256), 0, s, k, out);
+    return (int)hipGetLastError();
+}
+
+int ofdm_devtest_decide(int k, const double* z, const double* tau, uint8_t* sel, uint8_t* thr, long n,
+                        hipStream_t s)
+{
+    if (k != 2 && k != 4) return -1;
+    if (n <= 0) return 0;
+    const dim3 grid((unsigned)((n + 255) / 256));
+    const double2* zz = reinterpret_cast<const double2*>(z);
+    if (k == 2)
+        hipLaunchKernelGGL(decide_kernel<2>, grid, dim3(256), 0, s, zz, tau, sel, thr, n);
+    else
+        hipLaunchKernelGGL(decide_kernel<4>, grid, dim3(256), 0, s, zz, tau, sel, thr, n);
+    return (int)hipGetLastError();
+}
+
+int ofdm_devtest_emit_words(int k, const unsigned* bits, unsigned* words, int nwaves, hipStream_t s)
+{
+    if (k != 2 && k != 4) return -1;
+    if (nwaves <= 0) return 0;
+    if (k == 2)
+        hipLaunchKernelGGL(emit_words_kernel<2>, dim3(nwaves), dim3(64), 0, s, bits, words);
+    else
+        hipLaunchKernelGGL(emit_words_kernel<4>, dim3(nwaves), dim3(64), 0, s, bits, words);
+    return (int)hipGetLastError();
+}
 
 int ofdm_devtest_atan2(const double* y, const double* x, double* out, long n, hipStream_t s)
 {

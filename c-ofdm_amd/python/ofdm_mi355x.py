@@ -88,6 +88,7 @@ SIGNATURES = {
     "ofdm_create": (_I, [_PP, _I, C.POINTER(_V)]),
     "ofdm_destroy": (_I, [_V]),
     "ofdm_get_geometry": (_I, [_V, C.POINTER(Geometry)]),
+    "ofdm_rx_emit_fast": (_I, [_V]),
     "ofdm_get_t2_symbol": (_I, [_V, _V]),
     "ofdm_get_preamble": (_I, [_V, _V, _V, _V, _V]),
     "ofdm_device_alloc": (_I, [_V, _SZ, C.POINTER(_V)]),
@@ -273,6 +274,10 @@ class Modem:
             self.close()
         except Exception:
             pass
+
+    def rx_emit_fast(self) -> bool:
+        """True if rx takes the threshold-compare emit where a launch allows it."""
+        return lib().ofdm_rx_emit_fast(self.h) == 1
 
     # ---- constants
     def t2_symbol(self):

@@ -153,6 +153,11 @@ int ofdm_config_lookup(const char* path, const char* key, long* value);
 int ofdm_create(const ofdm_params* params, int device, ofdm_ctx** out);
 int ofdm_destroy(ofdm_ctx* ctx);
 int ofdm_get_geometry(const ofdm_ctx* ctx, ofdm_geometry* out);
+/* 1 if this context's batched rx takes the threshold-compare emit (QPSK; the
+ * decision thresholds were found and verified on the device at creation)
+ * wherever a launch's arguments allow it, 0 if it keeps the decision
+ * arithmetic, negative for a null context. */
+int ofdm_rx_emit_fast(const ofdm_ctx* ctx);
 /* Host copies of the constant frame parts (for FRAME_FORM::buf, get(), preamble.*). */
 int ofdm_get_t2_symbol(const ofdm_ctx* ctx, double* out /* t2sin_size complex */);
 int ofdm_get_preamble(const ofdm_ctx* ctx,

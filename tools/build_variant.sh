@@ -11,11 +11,13 @@ SRC=${SRC:-$R}  # source tree (e.g. an exported older commit)
 B=$R/abtest/build_$NAME
 mkdir -p $B $R/abtest
 H="/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-result -munsafe-fp-atomics -I$SRC/include $FLAGS"
-$H -c $SRC/c-ofdm_amd/csrc/ofdm_kernels.hip -o $B/k.o &
-$H -c $SRC/c-ofdm_amd/csrc/ofdm_sync.hip -o $B/s.o &
-[ -f $SRC/c-ofdm_amd/csrc/ofdm_stream_wide.hip ] && $H -c $SRC/c-ofdm_amd/csrc/ofdm_stream_wide.hip -o $B/w.o &
-$H -x hip -c $SRC/c-ofdm_amd/csrc/ofdm_capi.cpp -o $B/c.o &
-wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o $R/abtest/libofdm_$NAME.so $B/*.o
+# every device source of the tree being built (an older commit may have fewer)
+pids=()
+for f in $SRC/c-ofdm_amd/csrc/*.hip; do
+  $H -c $f -o $B/$(basename $f .hip).o & pids+=($!)
+done
+$H -x hip -c $SRC/c-ofdm_amd/csrc/ofdm_capi.cpp -o $B/ofdm_capi.o & pids+=($!)
+for p in "${pids[@]}"; do wait $p; done
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o $R/abtest/libofdm_$NAME.so $B/*.o -ldl
 rm -rf $B
 echo built abtest/libofdm_$NAME.so
