@@ -377,15 +377,7 @@ int ofdm_destroy(ofdm_ctx* c)
     return OFDM_OK;
 }
 
-static std::vector<double2> twiddles(int n)
-{
-    std::vector<double2> w(n);
-    for (int j = 0; j < n; ++j) {
-        const double a = 2.0 * M_PI * (double)j / (double)n;
-        w[j] = make_double2(std::cos(a), -std::sin(a));
-    }
-    return w;
-}
+using ofdm::twiddles;  // ofdm_internal.hpp
 
 // Modulation::Modulation table (modulation.cpp:4-36).
 static std::vector<double2> constellation(int k)

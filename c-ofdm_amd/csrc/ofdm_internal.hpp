@@ -2,9 +2,25 @@
 // by ofdm_kernels.hip (device code) and ofdm_capi.cpp (the C-ABI).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstdint>
+#include <vector>
 
 namespace ofdm {
+
+// The forward twiddle table W_n^j = exp(-2*pi*i*j/n), j < n, of every FFT
+// context (DevTables::tw and the sync kernels' tables; load_twiddles builds
+// the two-level LDS table from it). Host code; shared with the test-only
+// launchers (devtest/ofdm_devtest.hip), so the table is under test too.
+inline std::vector<double2> twiddles(int n)
+{
+    std::vector<double2> w(n);
+    for (int j = 0; j < n; ++j) {
+        const double a = 2.0 * M_PI * (double)j / (double)n;
+        w[j] = make_double2(std::cos(a), -std::sin(a));
+    }
+    return w;
+}
 
 // Per-context constant tables, resident in HBM (tiny; L2-resident in practice).
 struct DevTables {

@@ -2588,7 +2588,10 @@ __global__ void __launch_bounds__(WalkShape<LOGT>::WT, 4) stream_walk_kernel(Wal
                     OFDM_PHASE(t2_step32_fft);
                     fft_regs_wave32p<LOGT, -1>(v, tt, lds_tw, fftb32 + g * N);
                     OFDM_PHASE(t2_step32_sums);
-                    // per block: total energy and detector-bin energy (packed A | B)
+                    // per block: total energy and detector-bin energy (packed A | B).
+                    // The mask bits above, these sums and the screen rule have a replica in
+                    // devtest/ofdm_devtest.hip (fft32p_kernel), on which the ratio's error is
+                    // measured; tests/test_gpu_t2_near_level.py ties the two together.
                     pf2 tot2 = {0.f, 0.f}, sin2 = {0.f, 0.f};
                     int mb;
                     asm volatile("v_mov_b32 %0, %1" : "=v"(mb) : "v"(mbits));

@@ -120,7 +120,7 @@ def distance_to_threshold(k, pts):
     return np.minimum(dre, dim)
 
 
-def check_stream_frames(cfg, x, pbs, got_bytes, got_cons, got_cfo=None, tol=1e-9, allow_flips=False):
+def check_stream_frames(cfg, x, pbs, got_bytes, got_cons, got_cfo=None, tol=1e-9, allow_flips=False, threads=0):
     """Every located frame of a stream against the oracle's main.cpp:60-80
     chain on the same samples (orc_decode_frames): CFO exact, constellation
     within `tol` relative per frame, and every byte equal, except that a
@@ -128,12 +128,13 @@ def check_stream_frames(cfg, x, pbs, got_bytes, got_cons, got_cfo=None, tol=1e-9
     band of its threshold (twice the largest GPU-oracle point difference of
     the whole stream: the sync chain's transcendentals and the FFT round
     differently). With allow_flips False (the default) no
-    decision may differ at all: north_star's bit-exact decisions. Returns a
-    summary dict."""
+    decision may differ at all: north_star's bit-exact decisions. `threads`:
+    the oracle's decode threads (0 = one per CPU; a test that checks many
+    short streams passes a small number). Returns a summary dict."""
     k = cfg["mod_type"]
     g = O.geometry(cfg)
     nf = len(pbs)
-    ocfo, ocons, obytes = O.decode_frames(cfg, x, pbs)
+    ocfo, ocons, obytes = O.decode_frames(cfg, x, pbs, threads=threads)
     if got_cfo is not None:
         bad = np.nonzero(got_cfo != ocfo)[0]
         assert bad.size == 0, f"CFO differs on {bad.size} frames, first {bad[:8]}"
