@@ -135,6 +135,15 @@ struct ofdm_ctx {
     int* d_rx_pack = nullptr;
     int* d_pilot_swz = nullptr;
     int* d_tx_code = nullptr;
+    // tx dead-group masks (ofdm_internal.hpp tx_dead_masks); d_tx_dead stays
+    // null when no wave has a dead group. tx_sparse: ofdm_tx_sparse's switch
+    std::vector<int> tx_code;
+    std::vector<unsigned> tx_dead;
+    unsigned* d_tx_dead = nullptr;
+#ifndef OFDM_TX_SPARSE_DEFAULT  // 0: an A/B build (tools/build_variant.sh) that maps every group
+#define OFDM_TX_SPARSE_DEFAULT 1
+#endif
+    bool tx_sparse = OFDM_TX_SPARSE_DEFAULT != 0;
     double2* d_const = nullptr;
     double2* d_const_bpsk = nullptr;
     // decide_select's thresholds (the rx emit's fast path, k = 2), found on
@@ -350,7 +359,7 @@ int ofdm_destroy(ofdm_ctx* c)
     if (!c) return OFDM_OK;
     (void)hipSetDevice(c->device);
     void* ptrs[] = {c->d_tw, c->d_data_bin, c->d_data_slot, c->d_pilot_bin, c->d_bin_map, c->d_rx_pack,
-                    c->d_pilot_swz, c->d_tx_code, c->d_const,
+                    c->d_pilot_swz, c->d_tx_code, c->d_tx_dead, c->d_const,
                     c->d_const_bpsk, c->d_header, c->d_preamble, c->d_templ, c->d_tspec, c->d_tspec32, c->d_twm, c->d_modpre,
                     c->d_t2mask,
                     c->d_t2tw, c->d_first, c->d_scratch, c->d_cfo_scratch, c->d_pre_hv, c->d_pre_done};
@@ -473,6 +482,13 @@ int ofdm_create(const ofdm_params* params, int device, ofdm_ctx** out)
     for (int b = 0; b < c->N; ++b)
         tx_code[b] = bin_map[b] >= 0 ? ofdm::tx_code_data(bin_map[b])
                                      : ofdm::tx_code_fixed(bin_map[b] == -2 ? ofdm::TX_LDS_PILOT : ofdm::TX_LDS_ZERO);
+    c->tx_code = tx_code;
+    c->tx_dead = ofdm::tx_dead_masks(tx_code);
+    if (std::any_of(c->tx_dead.begin(), c->tx_dead.end(), [](unsigned m) { return m != 0; }) &&
+        (rc = upload(&c->d_tx_dead, c->tx_dead))) {
+        ofdm_destroy(c);
+        return rc;
+    }
     if ((rc = upload(&c->d_rx_pack, rx_pack)) || (rc = upload(&c->d_pilot_swz, pilot_swz)) ||
         (rc = upload(&c->d_tx_code, tx_code)) ||
         (rc = upload(&c->d_tw, twiddles(c->N))) || (rc = upload(&c->d_data_bin, data_bin)) ||
@@ -771,6 +787,15 @@ int ofdm_get_geometry(const ofdm_ctx* c, ofdm_geometry* o)
 
 int ofdm_rx_emit_fast(const ofdm_ctx* c) { return c ? (c->dec_fast ? 1 : 0) : -1; }
 
+int ofdm_tx_sparse(ofdm_ctx* c, int enable, unsigned* masks_out, int* codes_out)
+{
+    if (!c) return -1;
+    if (enable >= 0) c->tx_sparse = enable != 0;
+    if (masks_out) std::copy(c->tx_dead.begin(), c->tx_dead.end(), masks_out);
+    if (codes_out) std::copy(c->tx_code.begin(), c->tx_code.end(), codes_out);
+    return c->tx_sparse && c->d_tx_dead ? 1 : 0;
+}
+
 int ofdm_get_t2_symbol(const ofdm_ctx* c, double* o)
 {
     if (!c || !o) return fail(OFDM_ERR_INVALID, "null argument");
@@ -934,6 +959,7 @@ static void fill_tx(const ofdm_ctx* c, ofdm::TxArgs& a, const uint8_t* bytes, si
                     size_t stride, int16_t* iq16, const ofdm_channel* ch)
 {
     a.tab = c->tables(false);
+    a.tx_dead = c->tx_sparse ? c->d_tx_dead : nullptr;
     a.bytes = bytes;
     a.iq = reinterpret_cast<double2*>(iq);
     a.iq16 = iq16;

@@ -280,13 +280,53 @@ __device__ __forceinline__ void dft4(double2& a0, double2& a1, double2& a2, doub
     a3 = csub(t1, t3);
 }
 
-template <int SIGN>
+// dft4 with inputs known to be +0: Z1: a1, Z2: a2. The additions and
+// subtractions of those zeros are dropped and nothing else changes:
+// t0 = t1 = a0 when a2 is zero; t2 = a3 and t3 = -(SIGN*i) a3 when a1 is,
+// the negation folded into the two operations that consume t3 (x - y and
+// x + (-y) round alike). Exact while no live input is -0, which a +0 added
+// to it would have turned into +0.
+template <int SIGN, bool Z1, bool Z2>
+__device__ __forceinline__ void dft4z(double2& a0, double2& a1, double2& a2, double2& a3)
+{
+    const double2 t0 = Z2 ? a0 : cadd(a0, a2), t1 = Z2 ? a0 : csub(a0, a2);
+    if constexpr (Z1) {
+        const double2 t2 = a3, j3 = mul_j<SIGN>(a3);
+        a0 = cadd(t0, t2);
+        a1 = csub(t1, j3);
+        a2 = csub(t0, t2);
+        a3 = cadd(t1, j3);
+    } else {
+        const double2 t2 = cadd(a1, a3), t3 = mul_j<SIGN>(csub(a1, a3));
+        a0 = cadd(t0, t2);
+        a1 = cadd(t1, t3);
+        a2 = csub(t0, t2);
+        a3 = csub(t1, t3);
+    }
+}
+
+// Inputs of a radix-8 butterfly known to be +0 (the tx kernel's first pass:
+// whole register groups of a wave that lie in the guard band).
+enum Dft8Zeros {
+    DFT8_FULL = 0,
+    DFT8_Z2345 = 0x3c,  // x2..x5
+    DFT8_Z34 = 0x18,    // x3, x4
+};
+
+template <int SIGN, int ZEROS = DFT8_FULL>
 __device__ __forceinline__ void dft8(double2& x0, double2& x1, double2& x2, double2& x3,
                                      double2& x4, double2& x5, double2& x6, double2& x7)
 {
+    static_assert(ZEROS == DFT8_FULL || ZEROS == DFT8_Z2345 || ZEROS == DFT8_Z34, "no pruned form for this pattern");
     constexpr double C = 0.70710678118654752440084436210484903928483593768847;
-    dft4<SIGN>(x0, x2, x4, x6);  // E0..E3
-    dft4<SIGN>(x1, x3, x5, x7);  // O0..O3
+    constexpr bool z2 = (ZEROS >> 2) & 1, z3 = (ZEROS >> 3) & 1, z4 = (ZEROS >> 4) & 1, z5 = (ZEROS >> 5) & 1;
+    if constexpr (ZEROS == DFT8_FULL) {
+        dft4<SIGN>(x0, x2, x4, x6);  // E0..E3
+        dft4<SIGN>(x1, x3, x5, x7);  // O0..O3
+    } else {
+        dft4z<SIGN, z2, z4>(x0, x2, x4, x6);
+        dft4z<SIGN, z3, z5>(x1, x3, x5, x7);
+    }
     // O1 *= W8, O2 *= W8^2 = SIGN*i, O3 *= W8^3
     const double2 o1 = make_double2((x3.x - SIGN * x3.y) * C, (x3.y + SIGN * x3.x) * C);
     const double2 o2 = mul_j<SIGN>(x5);
@@ -513,6 +553,19 @@ __device__ __forceinline__ void fft_regs(double2 (&v)[8], int t, const double2* 
     static_assert(LOGN >= 6 && LOGN <= 12, "N must be 64..4096");
     stockham_pass<LOGN, 8, 1, SIGN>(v, t, lds_tw, lds);
     fft_regs_tail<LOGN, 1, SIGN>(v, t, lds_tw, lds);
+}
+
+// The first pass of fft_regs (span 1: no twiddles, one radix-8 butterfly over
+// v[0..7]) for inputs of which the v[i] named by ZEROS are +0 and are not
+// read; fft_regs_tail<LOGN, 1, SIGN> completes the transform.
+template <int LOGN, int SIGN, int ZEROS>
+__device__ __forceinline__ void fft_regs_first(double2 (&v)[8], int t, double2* __restrict__ lds)
+{
+    static_assert(LOGN >= 6 && LOGN <= 12, "N must be 64..4096");
+    dft8<SIGN, ZEROS>(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]);
+    // stockham_apply's write for R = 8, NS = 1: output r of butterfly t to index 8t + r
+#pragma unroll
+    for (int r = 0; r < 8; ++r) lds[lds_swz(8 * t + r)] = v[r];
 }
 
 // fft_regs run by the first N/8 threads of a larger workgroup (`active`

@@ -55,6 +55,8 @@ struct TxArgs {
     double noise_scale;         // noise_std / sqrt(2)
     unsigned long long seed;
     unsigned long long sample_offset;
+    // one mask per wave of the workgroup (tx_dead_masks); null: every group is mapped
+    const unsigned* tx_dead;
 };
 
 // The staged stream decode's ramp table, per frame and message symbol:
@@ -138,6 +140,24 @@ constexpr int RX_WAVES_PER_CU = 8;
 constexpr int TX_LDS_PILOT = 256, TX_LDS_ZERO = 257;
 inline int tx_code_data(int d) { return d | (0xff << 13); }
 inline int tx_code_fixed(int entry) { return entry << 21; }
+// tx dead groups: thread t of the N/8 holds bins t + (N/8) i, i < 8, so wave w
+// holds, as its register group i, the 64 bins 64 w + lane + (N/8) i. Bit i of
+// mask w is set when all of them are TX_LDS_ZERO entries (guard band or bin
+// 0): the kernel then neither loads nor maps the group, and its first
+// butterfly drops the additions of those zeros. No masks for N < 512 (less
+// than a wave of threads).
+inline std::vector<unsigned> tx_dead_masks(const std::vector<int>& tx_code)
+{
+    const int T = (int)tx_code.size() / 8;
+    std::vector<unsigned> m(T / 64, 0u);
+    for (int w = 0; w < T / 64; ++w)
+        for (int i = 0; i < 8; ++i) {
+            bool dead = true;
+            for (int lane = 0; lane < 64; ++lane) dead = dead && tx_code[64 * w + lane + T * i] == tx_code_fixed(TX_LDS_ZERO);
+            if (dead) m[w] |= 1u << i;
+        }
+    return m;
+}
 // tx: persistent grid-stride launch size (symbols per workgroup = nsym / grid)
 constexpr long TX_MAX_GRID = 4096;
 

@@ -219,8 +219,8 @@ __device__ __forceinline__ unsigned long long block_sum_u64(unsigned long long v
 // NOISE / I16: fused AWGN and int16 wire output compiled in (a.noise_scale > 0,
 // a.iq16 != nullptr), so each variant gets its own register allocation.
 // Workgroups per CU the register allocation is bounded for: 4 at N = 2048
-// with f64 output (128 VGPRs, ~36 dwords spilled; 3 per CU at the unbounded
-// 163 VGPRs): tx 0.556 -> 0.545 ms in the bench step, same box
+// with f64 output (126 VGPRs and no scratch under the bound; 3 per CU
+// unbounded): tx 0.556 -> 0.545 ms in the bench step, same box
 // (profiles/r03z_tx_occupancy.txt). Other shapes and the int16 output keep
 // the compiler's choice.
 constexpr int tx_min_blocks(int logn, bool i16) { return logn == 11 && !i16 ? 4 : 1; }
@@ -253,10 +253,7 @@ __global__ void __launch_bounds__((1 << LOGN) / 8, tx_min_blocks(LOGN, I16)) tx_
     const int k = a.k;
     const int bps = a.D * k / 8;  // payload bytes per symbol (host checks D*k % 8 == 0)
     const int L = N + a.cp;
-    auto sym_bytes = [&](long sym) {
-        const long f = sym / a.S;
-        return a.bytes + f * a.bytes_per_frame + (sym - f * a.S) * bps;
-    };
+    auto sym_bytes = [&](long f, int s) { return a.bytes + f * a.bytes_per_frame + (long)s * bps; };
     // Payload prefetch, written to LDS only after the FFT so the loads' latency
     // hides behind it: 32-bit words t and t + T when every symbol's payload is
     // word aligned (bps <= N bytes = 2T words), else bytes t + T*r. Indices are
@@ -265,8 +262,7 @@ __global__ void __launch_bounds__((1 << LOGN) / 8, tx_min_blocks(LOGN, I16)) tx_
     const bool by_word = (bps & 3) == 0 && (a.bytes_per_frame & 3) == 0 && ((uintptr_t)a.bytes & 3) == 0;
     const int nwords = bps >> 2;
     uint32_t nb[8];
-    auto fetch = [&](long s) {
-        const uint8_t* src = sym_bytes(s);
+    auto fetch = [&](const uint8_t* src) {
         if (by_word) {
             // word indices from an opaque copy of the thread index (not held
             // across the symbol loop)
@@ -292,9 +288,15 @@ __global__ void __launch_bounds__((1 << LOGN) / 8, tx_min_blocks(LOGN, I16)) tx_
         }
     };
 
+    // (frame, symbol) of `sym`, advanced incrementally: the loop has no 64-bit
+    // division, the next symbol's payload address included
     long sym = blockIdx.x;
+    const long gstep_f = gridDim.x / a.S;
+    const int gstep_s = (int)(gridDim.x - gstep_f * a.S);
+    long f = sym / a.S;
+    int s = (int)(sym - f * a.S);
     if (!POINTS && sym < nsym) {
-        fetch(sym);
+        fetch(sym_bytes(f, s));
         publish();
     }
     lds_barrier();  // twiddle table + first payload visible
@@ -305,41 +307,74 @@ __global__ void __launch_bounds__((1 << LOGN) / 8, tx_min_blocks(LOGN, I16)) tx_
     const int i_cp = 8 - a.cp / T;
     const int kmask = (1 << k) - 1;
 
-    // (frame, symbol) of `sym`, advanced incrementally (no 64-bit division in the loop)
-    const long gstep_f = gridDim.x / a.S;
-    const int gstep_s = (int)(gridDim.x - gstep_f * a.S);
-    long f = sym / a.S;
-    int s = (int)(sym - f * a.S);
-    for (; sym < nsym; sym += gridDim.x) {
-        // Modulation::mod: k-bit symbol -> constellation point (modulation.cpp:39-50);
-        // pilots = pilot_ampl, unused bins 0 (Frame.cpp:56-62)
-        double2 v[8];
-        int code[8];
-        {
-            // opaque copy of the thread index: the loads stay in the loop
-            int tt;
-            asm volatile("v_mov_b32 %0, %1" : "=v"(tt) : "v"(t));
-            const int* ct = a.tab.tx_code + tt;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) code[i] = ct[T * i];
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int d = code[i] & 0x1fff, m = (code[i] >> 13) & 0xff, base = code[i] >> 21;
-            if constexpr (POINTS) {
-                v[i] = m ? a.points[sym * a.D + d] : lds_const[base];
-            } else {
-                const int bit = d * k;
-                const int byte = bit >> 3, off = bit & 7;
-                const int w = ((int)sbytes[byte] << 8) | (int)sbytes[byte + 1];
-                v[i] = lds_const[((w >> (16 - off - k)) & kmask & m) + base];
-            }
-        }
-        const long nxt = sym + gridDim.x;
-        if constexpr (!POINTS) fetch(nxt < nsym ? nxt : sym);
+    // this wave's dead groups (ofdm_internal.hpp tx_dead_masks): a scalar
+    unsigned dead = 0;
+    if constexpr (T >= 64) {
+        if (a.tx_dead) dead = __builtin_amdgcn_readfirstlane(a.tx_dead[t >> 6]);
+    }
 
-        // unnormalised backward DFT (Frame.cpp:64); v[i] = x[t + T*i] on exit
-        fft_regs<LOGN, +1>(v, t, lds_tw, fft);
+    for (; sym < nsym; sym += gridDim.x) {
+        long fn = f + gstep_f;
+        int sn = s + gstep_s;
+        if (sn >= a.S) {
+            sn -= a.S;
+            ++fn;
+        }
+        const bool more = sym + gridDim.x < nsym;
+        // Modulation::mod: k-bit symbol -> constellation point (modulation.cpp:39-50);
+        // pilots = pilot_ampl, unused bins 0 (Frame.cpp:56-62); then the next
+        // payload's prefetch and the transform's first pass. ZEROS: register
+        // groups of this wave that hold unused bins only: no code load, no
+        // stage or table read, and a first butterfly without their additions.
+        double2 v[8];
+        auto map_first = [&](auto zeros) {
+            constexpr int ZEROS = decltype(zeros)::value;
+            int code[8];
+            {
+                // opaque copy of the thread index: the loads stay in the loop
+                int tt;
+                asm volatile("v_mov_b32 %0, %1" : "=v"(tt) : "v"(t));
+                const int* ct = a.tab.tx_code + tt;
+#pragma unroll
+                for (int i = 0; i < 8; ++i)
+                    if (!((ZEROS >> i) & 1)) code[i] = ct[T * i];
+            }
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                if ((ZEROS >> i) & 1) {
+                    v[i] = make_double2(0.0, 0.0);
+                    continue;
+                }
+                const int d = code[i] & 0x1fff, m = (code[i] >> 13) & 0xff, base = code[i] >> 21;
+                if constexpr (POINTS) {
+                    v[i] = m ? a.points[sym * a.D + d] : lds_const[base];
+                } else {
+                    const int bit = (int)__umul24((unsigned)d, (unsigned)k);  // d < 2^13, k <= 8: full rate
+                    const int byte = bit >> 3, off = bit & 7;
+                    const int w = ((int)sbytes[byte] << 8) | (int)sbytes[byte + 1];
+                    v[i] = lds_const[((w >> (16 - off - k)) & kmask & m) + base];
+                }
+            }
+            if constexpr (!POINTS) fetch(more ? sym_bytes(fn, sn) : sym_bytes(f, s));
+            // unnormalised backward DFT (Frame.cpp:64), first pass
+            if constexpr (ZEROS == DFT8_FULL)
+                stockham_pass<LOGN, 8, 1, +1>(v, t, lds_tw, fft);
+            else
+                fft_regs_first<LOGN, +1, ZEROS>(v, t, fft);
+        };
+        // a pruned form may treat a dead group as live, never the reverse
+        if constexpr (T >= 64) {
+            if ((dead & DFT8_Z2345) == DFT8_Z2345)
+                map_first(std::integral_constant<int, DFT8_Z2345>());
+            else if ((dead & DFT8_Z34) == DFT8_Z34)
+                map_first(std::integral_constant<int, DFT8_Z34>());
+            else
+                map_first(std::integral_constant<int, DFT8_FULL>());
+        } else {
+            map_first(std::integral_constant<int, DFT8_FULL>());
+        }
+        // the remaining passes; v[i] = x[t + T*i] on exit
+        fft_regs_tail<LOGN, 1, +1>(v, t, lds_tw, fft);
         // Publish the next payload now, before this symbol's stores: on gfx9
         // vmcnt also counts stores, so a wait on these loads placed after the
         // stores would drain them every symbol. Every thread has mapped this
@@ -404,12 +439,8 @@ __global__ void __launch_bounds__((1 << LOGN) / 8, tx_min_blocks(LOGN, I16)) tx_
             }
         }
         lds_barrier();  // next payload visible; the last pass's LDS reads precede the next pass 0
-        s += gstep_s;
-        f += gstep_f;
-        if (s >= a.S) {
-            s -= a.S;
-            ++f;
-        }
+        f = fn;
+        s = sn;
     }
 }
 

@@ -89,6 +89,7 @@ SIGNATURES = {
     "ofdm_destroy": (_I, [_V]),
     "ofdm_get_geometry": (_I, [_V, C.POINTER(Geometry)]),
     "ofdm_rx_emit_fast": (_I, [_V]),
+    "ofdm_tx_sparse": (_I, [_V, _I, _V, _V]),
     "ofdm_get_t2_symbol": (_I, [_V, _V]),
     "ofdm_get_preamble": (_I, [_V, _V, _V, _V, _V]),
     "ofdm_device_alloc": (_I, [_V, _SZ, C.POINTER(_V)]),
@@ -278,6 +279,20 @@ class Modem:
     def rx_emit_fast(self) -> bool:
         """True if rx takes the threshold-compare emit where a launch allows it."""
         return lib().ofdm_rx_emit_fast(self.h) == 1
+
+    def tx_sparse(self, enable: bool | None = None) -> bool:
+        """ofdm_tx_sparse: switch tx's dead-group skipping (None: leave it);
+        True if tx skips dead groups now."""
+        return lib().ofdm_tx_sparse(self.h, -1 if enable is None else int(enable), None, None) == 1
+
+    def tx_dead_tables(self):
+        """(masks, codes): tx's per-wave dead-group masks (fft_size/512 words)
+        and the per-bin codes they were built from."""
+        import numpy as np
+        n = self.params.fft_size
+        masks, codes = np.zeros(n // 512, np.uint32), np.zeros(n, np.int32)
+        lib().ofdm_tx_sparse(self.h, -1, masks.ctypes.data, codes.ctypes.data)
+        return masks, codes
 
     # ---- constants
     def t2_symbol(self):

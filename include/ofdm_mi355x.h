@@ -158,6 +158,17 @@ int ofdm_get_geometry(const ofdm_ctx* ctx, ofdm_geometry* out);
  * wherever a launch's arguments allow it, 0 if it keeps the decision
  * arithmetic, negative for a null context. */
 int ofdm_rx_emit_fast(const ofdm_ctx* ctx);
+/* tx's dead groups: a wave of the tx kernel whose 64 bins of one register
+ * group all lie in the guard band skips that group's mapping, and its first
+ * butterfly drops the additions of those zeros (same samples; fft_size >= 512).
+ * enable = 0 makes this context's tx map every group as before, 1 switches
+ * the skipping back on (the default), negative leaves the switch alone.
+ * masks_out (nullable, fft_size/512 words) receives the per-wave masks (bit i:
+ * bins 64 w + lane + (fft_size/8) i are all unused), codes_out (nullable,
+ * fft_size ints) the per-bin codes they were built from (bits 21..29 = 257
+ * for an unused bin). Returns 1 if tx skips dead groups now (switched on and
+ * some mask non-zero), 0 if not, negative for a null context. */
+int ofdm_tx_sparse(ofdm_ctx* ctx, int enable, unsigned* masks_out, int* codes_out);
 /* Host copies of the constant frame parts (for FRAME_FORM::buf, get(), preamble.*). */
 int ofdm_get_t2_symbol(const ofdm_ctx* ctx, double* out /* t2sin_size complex */);
 int ofdm_get_preamble(const ofdm_ctx* ctx,
