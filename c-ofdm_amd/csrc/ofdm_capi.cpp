@@ -36,16 +36,16 @@ static constexpr int kRcclInt64 = ncclInt64, kRcclSum = ncclSum;
 static constexpr int kRcclInt64 = 4, kRcclSum = 0;  // rccl.h: ncclInt64, ncclSum (header absent at build time)
 #endif
 #include "ofdm_csi.hpp"
+#include "ofdm_ctx.hpp"
 #include "ofdm_internal.hpp"
 #include "ofdm_sync.hpp"
 
-using cd = std::complex<double>;
-
 namespace {
-
 thread_local std::string g_err;
+}
 
-int fail(int code, const char* fmt, ...)
+// (declared in ofdm_ctx.hpp: ofdm_stream_call.cpp reports errors the same way)
+int ofdm::fail(int code, const char* fmt, ...)
 {
     char buf[512];
     va_list ap;
@@ -56,16 +56,22 @@ int fail(int code, const char* fmt, ...)
     return code;
 }
 
-int hip_fail(hipError_t e, const char* what)
+int ofdm::hip_fail(hipError_t e, const char* what)
 {
     return fail(OFDM_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
 }
 
-#define HIP_TRY(expr)                                   \
-    do {                                                \
-        hipError_t _e = (expr);                         \
-        if (_e != hipSuccess) return hip_fail(_e, #expr); \
-    } while (0)
+using ofdm::aligned16;
+using ofdm::capture_refused;
+using ofdm::capturing;
+using ofdm::cfo_plan;
+using ofdm::fail;
+using ofdm::grow;
+using ofdm::grow_host;
+using ofdm::hip_fail;
+using ofdm::initial_state;
+
+namespace {
 
 int ilog2_exact(long n)
 {
@@ -115,129 +121,111 @@ int upload(T** dst, const std::vector<T>& v)
 
 }  // namespace
 
-// --------------------------------------------------------------------------
-struct ofdm_ctx {
-    ofdm_params p{};
-    int device = 0;
-    int logn = 0;
-    int N = 0, D = 0, P = 0, cp = 0, S = 0, k = 0, L = 0, seg = 0, npr = 0, t2 = 0;
-    ofdm_geometry geo{};
-    // host constants
-    std::vector<cd> t2_symbol, ofdm_preamble, mod_preamble, templ;
-    std::vector<uint8_t> preamble_bytes;
-    std::vector<double> t2_mask;
-    // device tables
-    double2* d_tw = nullptr;
-    int* d_data_bin = nullptr;
-    int* d_data_slot = nullptr;
-    int* d_pilot_bin = nullptr;
-    int* d_bin_map = nullptr;
-    int* d_rx_pack = nullptr;
-    int* d_pilot_swz = nullptr;
-    int* d_tx_code = nullptr;
-    // tx dead-group masks (ofdm_internal.hpp tx_dead_masks); d_tx_dead stays
-    // null when no wave has a dead group. tx_sparse: ofdm_tx_sparse's switch
-    std::vector<int> tx_code;
-    std::vector<unsigned> tx_dead;
-    unsigned* d_tx_dead = nullptr;
-#ifndef OFDM_TX_SPARSE_DEFAULT  // 0: an A/B build (tools/build_variant.sh) that maps every group
-#define OFDM_TX_SPARSE_DEFAULT 1
-#endif
-    bool tx_sparse = OFDM_TX_SPARSE_DEFAULT != 0;
-    double2* d_const = nullptr;
-    double2* d_const_bpsk = nullptr;
-    // decide_select's thresholds (the rx emit's fast path, k = 2), found on
-    // the device at creation; dec_fast = false: the scan's checks failed or
-    // k is not 2, and rx keeps the decision arithmetic
-    double dec_tau[3] = {};
-    bool dec_fast = false;
-    double2* d_header = nullptr;   // T2 + preamble
-    double2* d_preamble = nullptr; // ofdm_preamble (preamble_len)
-    double2* d_templ = nullptr;    // pr_sin_len
-    double2* d_tspec = nullptr;    // WALK_FFT_M template spectrum (stream walker FFT search)
-    float2* d_tspec32 = nullptr;   // the same rounded to FP32 (the search's FP32 tier)
-    double2* d_twm = nullptr;      // WALK_FFT_M twiddles
-    double tspec_max = 0.0;
-    double2* d_modpre = nullptr;   // D*npr
-    double* d_t2mask = nullptr;    // t2 size
-    double2* d_t2tw = nullptr;     // t2-size twiddles (T2 detector)
-    int* d_first = nullptr;        // T2 detector min-block scratch
-    int t2_logn = -1;              // T2sin_size = 2^t2_logn, else -1 (detector unsupported)
-    struct CfoPlan {               // pilot_freq_sinh on a form of nsym symbols
-        int nsym = 0, logm = -1, g = 0;
-        double2* tw_sub = nullptr;
-        double2* tw_full = nullptr;
-        int* borders = nullptr;
-    };
-    std::vector<CfoPlan> cfo_plans;
-    double* d_cfo_scratch = nullptr;
-    size_t cfo_scratch_n = 0;
-    // staged-rx scratch (grown on demand, only for num_symb > 8 or D > N/2)
-    double2* d_scratch = nullptr;
-    size_t scratch_bytes = 0;
-    // ofdm_rx_stream scratch (grown on demand): walker records, frame batch,
-    // channel estimates, frame starts
-    struct Grow {
-        void* p = nullptr;
-        size_t bytes = 0;
-    };
-    Grow s_walk, s_batch, s_chan, s_pbs;
-    // find_preamble's split form: magnitudes and per-start counters (zero
-    // between launches) for up to PRE_SCRATCH_STARTS start indices per call
-    static constexpr size_t PRE_SCRATCH_STARTS = 64;
-    double* d_pre_hv = nullptr;
-    unsigned* d_pre_done = nullptr;
-    // pinned host staging for the walk records and the frame list (pageable
-    // copies go through a driver bounce buffer and synchronise twice)
-    Grow h_walk, h_frames;
-    hipStream_t h_frames_stream = nullptr;  // stream of the last copy out of h_frames
-    bool h_frames_used = false;
-    int* d_queue = nullptr;        // walker chunk counter (zero between calls)
-    // rx dynamic-frame counters {next, done}, zero between launches: one slot
-    // per HIP stream that launched rx on this context (launches on one stream
-    // run in order, so each slot is reset by the launch before the next uses
-    // it); streams past RX_QUEUE_SLOTS run with a static frame order
-    static constexpr int RX_QUEUE_SLOTS = 32;
-    int* d_rxq = nullptr;          // RX_QUEUE_SLOTS x 16 ints (one 64-B line each)
-    hipStream_t rxq_stream[RX_QUEUE_SLOTS] = {};
-    bool rxq_live[RX_QUEUE_SLOTS] = {};  // slot bound to rxq_stream[i] (false: freed by ofdm_stream_destroy)
-    int rxq_used = 0;
-    ofdm_walk_tuning walk{};       // stream walker settings (ofdm_set_walk_tuning)
-    long ring = 0;                 // rx.cpp's SDR ring R (ofdm_set_stream_ring; 0: the continuous walk)
-    bool queue_zero = false;       // the last stream call's compaction left the walker counter zero
-    hipEvent_t ev_call = nullptr;  // recorded on call_stream when a stream call comes on another stream
-    hipStream_t call_stream = nullptr;  // the last stream call's HIP stream
-    bool call_valid = false;       //   (call_stream set)
-    hipEvent_t ev_walk = nullptr;  // walk records landed in h_walk
-    hipEvent_t ev_wdone = nullptr;  // the walk kernel finished (caller's stream)
-    hipStream_t side = nullptr;     // copies the walk records out beside the decode
-    // look-back walk: per-chunk publication counts (zero between calls: the
-    // resolve kernel clears them), the true walk's records for shard reports,
-    // and the resolve kernel's status block (page-locked, written by the kernel)
-    Grow s_pub, s_chain, h_status;
-    bool pub_zero = false;         // every s_pub word is zero
-    // per-phase device times of the last look-back stream call
-    // (ofdm_set_stream_timing): events before the walk, after the walk, after
-    // the resolve and after the decode, on the call's stream
-    bool phase_timing = false;
-    bool phase_valid = false;
-    hipEvent_t ev_phase[4] = {};
+using ofdm::twiddles;  // ofdm_internal.hpp
 
-    ofdm::DevTables tables(bool bpsk) const
-    {
-        ofdm::DevTables t;
-        t.tw = d_tw;
-        t.data_bin = d_data_bin;
-        t.data_slot = d_data_slot;
-        t.pilot_bin = d_pilot_bin;
-        t.bin_map = d_bin_map;
-        t.rx_pack = d_rx_pack;
-        t.pilot_swz = d_pilot_swz;
-        t.tx_code = d_tx_code;
-        t.constell = bpsk ? d_const_bpsk : d_const;
-        return t;
+// ---- the other helpers that ofdm_ctx.hpp declares ----
+
+// True while `st` is being captured into a hipGraph. Asked only on the paths
+// that are about to allocate, copy from pageable memory or synchronise (none
+// of which a capture allows), so that they can refuse before they break the
+// capture; the launches themselves never ask.
+bool ofdm::capturing(hipStream_t st)
+{
+    hipStreamCaptureStatus s = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &s) != hipSuccess) {
+        (void)hipGetLastError();  // (the legacy stream beside another stream's capture: not capturing)
+        return false;
     }
-};
+    return s != hipStreamCaptureStatusNone;
+}
+
+int ofdm::capture_refused(const char* what)
+{
+    return fail(OFDM_ERR_UNSUPPORTED, "%s: not possible on a stream that is being captured (make the same call once "
+                                      "before the capture)", what);
+}
+
+// pilot_freq_sinh plan for a form of nsym symbols: S = (N+cp)*nsym = M or 5*M,
+// M = 2^m; window borders exactly as Frame.hpp:311-321 computes them. A new
+// form length builds and uploads its tables (allocation, host copies): `st` is
+// the stream the caller will launch on, refused while it is being captured.
+int ofdm::cfo_plan(ofdm_ctx* c, int nsym, ofdm_ctx::CfoPlan** out, hipStream_t st)
+{
+    for (auto& pl : c->cfo_plans)
+        if (pl.nsym == nsym) {
+            *out = &pl;
+            return OFDM_OK;
+        }
+    if (capturing(st)) return capture_refused("the tables of a new CFO form length");
+    const long S = (long)c->L * nsym;
+    ofdm_ctx::CfoPlan pl;
+    pl.nsym = nsym;
+    if (ilog2_exact(S) >= 6 && ilog2_exact(S) <= 12) {
+        pl.g = 1;
+        pl.logm = ilog2_exact(S);
+    } else if (S % 5 == 0 && ilog2_exact(S / 5) >= 6 && ilog2_exact(S / 5) <= 10) {
+        pl.g = 5;
+        pl.logm = ilog2_exact(S / 5);
+    } else {
+        return fail(OFDM_ERR_UNSUPPORTED, "pilot_freq_sinh: form length %ld is not 2^a or 5*2^a (64 <= 2^a <= %d)", S,
+                    4096);
+    }
+    const int P = c->P;
+    const double rel_bw = double(c->D + c->P) / (c->N);
+    const double rel_pilot_w = rel_bw / P;
+    const int pilot_w = int(S * rel_pilot_w);
+    std::vector<int> borders(P + 2);
+    for (int i = 0, j = int((1.0 - rel_bw - rel_pilot_w) / 2.0 * S); i < P + 2; i++) {
+        borders[i] = j;
+        j += pilot_w;
+    }
+    borders[0] = std::max(0, borders[0]);
+    for (int b : borders)
+        if (b < 0 || b > S) return fail(OFDM_ERR_UNSUPPORTED, "pilot_freq_sinh windows leave the spectrum");
+    int rc;
+    if ((rc = upload(&pl.tw_sub, twiddles(1 << pl.logm))) || (rc = upload(&pl.borders, borders))) return rc;
+    if (pl.g == 5 && (rc = upload(&pl.tw_full, twiddles((int)S)))) return rc;
+    c->cfo_plans.push_back(pl);
+    *out = &c->cfo_plans.back();
+    return OFDM_OK;
+}
+
+bool ofdm::aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// Device scratch that only grows (contents not preserved).
+int ofdm::grow(ofdm_ctx* c, ofdm_ctx::Grow& g, size_t need)
+{
+    if (need <= g.bytes) return OFDM_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    if (g.p) HIP_TRY(hipFree(g.p));
+    g.p = nullptr;
+    g.bytes = 0;
+    HIP_TRY(hipMalloc(&g.p, need));
+    g.bytes = need;
+    return OFDM_OK;
+}
+
+// Pinned host staging that only grows (contents not preserved).
+int ofdm::grow_host(ofdm_ctx* c, ofdm_ctx::Grow& g, size_t need)
+{
+    if (need <= g.bytes) return OFDM_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    if (g.p) HIP_TRY(hipHostFree(g.p));
+    g.p = nullptr;
+    g.bytes = 0;
+    HIP_TRY(hipHostMalloc(&g.p, need, hipHostMallocDefault));
+    g.bytes = need;
+    return OFDM_OK;
+}
+
+// rx.cpp's initial walk state (rx.cpp:105-114): pos = 0 of a buffer whose
+// first output_size samples are the zero header before the first SDR buffer,
+// i.e. stream position -output_size in a ring ending at R; the continuous
+// walk starts at the stream's first sample.
+ofdm_walk_state ofdm::initial_state(const ofdm_ctx* c)
+{
+    return c->ring > 0 ? ofdm_walk_state{-c->geo.frame_len, c->ring} : ofdm_walk_state{0, 0};
+}
 
 extern "C" {
 
@@ -385,8 +373,6 @@ int ofdm_destroy(ofdm_ctx* c)
     delete c;
     return OFDM_OK;
 }
-
-using ofdm::twiddles;  // ofdm_internal.hpp
 
 // Modulation::Modulation table (modulation.cpp:4-36).
 static std::vector<double2> constellation(int k)
@@ -713,71 +699,6 @@ static void rx_queue_reset(ofdm_ctx* c, int* q, hipStream_t st)
     if (q) (void)hipMemsetAsync(q, 0, 2 * sizeof(int), st);
 }
 
-// True while `st` is being captured into a hipGraph. Asked only on the paths
-// that are about to allocate, copy from pageable memory or synchronise (none
-// of which a capture allows), so that they can refuse before they break the
-// capture; the launches themselves never ask.
-static bool capturing(hipStream_t st)
-{
-    hipStreamCaptureStatus s = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &s) != hipSuccess) {
-        (void)hipGetLastError();  // (the legacy stream beside another stream's capture: not capturing)
-        return false;
-    }
-    return s != hipStreamCaptureStatusNone;
-}
-
-static int capture_refused(const char* what)
-{
-    return fail(OFDM_ERR_UNSUPPORTED, "%s: not possible on a stream that is being captured (make the same call once "
-                                      "before the capture)", what);
-}
-
-// pilot_freq_sinh plan for a form of nsym symbols: S = (N+cp)*nsym = M or 5*M,
-// M = 2^m; window borders exactly as Frame.hpp:311-321 computes them. A new
-// form length builds and uploads its tables (allocation, host copies): `st` is
-// the stream the caller will launch on, refused while it is being captured.
-static int cfo_plan(ofdm_ctx* c, int nsym, ofdm_ctx::CfoPlan** out, hipStream_t st)
-{
-    for (auto& pl : c->cfo_plans)
-        if (pl.nsym == nsym) {
-            *out = &pl;
-            return OFDM_OK;
-        }
-    if (capturing(st)) return capture_refused("the tables of a new CFO form length");
-    const long S = (long)c->L * nsym;
-    ofdm_ctx::CfoPlan pl;
-    pl.nsym = nsym;
-    if (ilog2_exact(S) >= 6 && ilog2_exact(S) <= 12) {
-        pl.g = 1;
-        pl.logm = ilog2_exact(S);
-    } else if (S % 5 == 0 && ilog2_exact(S / 5) >= 6 && ilog2_exact(S / 5) <= 10) {
-        pl.g = 5;
-        pl.logm = ilog2_exact(S / 5);
-    } else {
-        return fail(OFDM_ERR_UNSUPPORTED, "pilot_freq_sinh: form length %ld is not 2^a or 5*2^a (64 <= 2^a <= %d)", S,
-                    4096);
-    }
-    const int P = c->P;
-    const double rel_bw = double(c->D + c->P) / (c->N);
-    const double rel_pilot_w = rel_bw / P;
-    const int pilot_w = int(S * rel_pilot_w);
-    std::vector<int> borders(P + 2);
-    for (int i = 0, j = int((1.0 - rel_bw - rel_pilot_w) / 2.0 * S); i < P + 2; i++) {
-        borders[i] = j;
-        j += pilot_w;
-    }
-    borders[0] = std::max(0, borders[0]);
-    for (int b : borders)
-        if (b < 0 || b > S) return fail(OFDM_ERR_UNSUPPORTED, "pilot_freq_sinh windows leave the spectrum");
-    int rc;
-    if ((rc = upload(&pl.tw_sub, twiddles(1 << pl.logm))) || (rc = upload(&pl.borders, borders))) return rc;
-    if (pl.g == 5 && (rc = upload(&pl.tw_full, twiddles((int)S)))) return rc;
-    c->cfo_plans.push_back(pl);
-    *out = &c->cfo_plans.back();
-    return OFDM_OK;
-}
-
 int ofdm_get_geometry(const ofdm_ctx* c, ofdm_geometry* o)
 {
     if (!c || !o) return fail(OFDM_ERR_INVALID, "null argument");
@@ -924,34 +845,6 @@ int ofdm_event_destroy(ofdm_ctx* c, void* ev)
 {
     if (!c) return fail(OFDM_ERR_INVALID, "null ctx");
     if (ev) HIP_TRY(hipEventDestroy((hipEvent_t)ev));
-    return OFDM_OK;
-}
-
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// Device scratch that only grows (contents not preserved).
-static int grow(ofdm_ctx* c, ofdm_ctx::Grow& g, size_t need)
-{
-    if (need <= g.bytes) return OFDM_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    if (g.p) HIP_TRY(hipFree(g.p));
-    g.p = nullptr;
-    g.bytes = 0;
-    HIP_TRY(hipMalloc(&g.p, need));
-    g.bytes = need;
-    return OFDM_OK;
-}
-
-// Pinned host staging that only grows (contents not preserved).
-static int grow_host(ofdm_ctx* c, ofdm_ctx::Grow& g, size_t need)
-{
-    if (need <= g.bytes) return OFDM_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    if (g.p) HIP_TRY(hipHostFree(g.p));
-    g.p = nullptr;
-    g.bytes = 0;
-    HIP_TRY(hipHostMalloc(&g.p, need, hipHostMallocDefault));
-    g.bytes = need;
     return OFDM_OK;
 }
 
@@ -1733,662 +1626,24 @@ int ofdm_sync_frames(ofdm_ctx* c, double* frames, size_t nframes, size_t stride,
     return OFDM_OK;
 }
 
-}  // extern "C"
-
-// rx.cpp's initial walk state (rx.cpp:105-114): pos = 0 of a buffer whose
-// first output_size samples are the zero header before the first SDR buffer,
-// i.e. stream position -output_size in a ring ending at R; the continuous
-// walk starts at the stream's first sample.
-static ofdm_walk_state initial_state(const ofdm_ctx* c)
-{
-    return c->ring > 0 ? ofdm_walk_state{-c->geo.frame_len, c->ring} : ofdm_walk_state{0, 0};
-}
-
-// ofdm_rx_stream / ofdm_rx_stream_i16 / ofdm_rx_stream_shard: exactly one of
-// iq, iq16 is set. The walk starts at state `start`; frames located with pb in
-// [own_lo, own_hi) are decoded (the whole stream: start = own_lo = 0, own_hi = n).
-static int rx_stream_impl(ofdm_ctx* c, const double* iq, const int16_t* iq16, size_t n, size_t max_frames,
-                          long chunk, long* pb_out, uint8_t* bytes_out, double* constell_out, double* cfo_out,
-                          size_t* nframes_out, void* stream, ofdm_walk_state start_state, long own_lo, long own_hi,
-                          long* located, uint8_t* located_lag, size_t located_cap, size_t* nlocated_out,
-                          ofdm_walk_state* exit_out, bool force_halo = false)
-{
-    if (!c || (!iq && !iq16) || !nframes_out) return fail(OFDM_ERR_INVALID, "null argument");
-    *nframes_out = 0;
-    if (nlocated_out) *nlocated_out = 0;
-    if (exit_out) *exit_out = ofdm_walk_state{-1, 0};
-    const long R = c->ring, flen0 = c->geo.frame_len;
-    const long start = start_state.pos;
-    // ring mode: the walk may start in rx.cpp's zero header before the first
-    // SDR buffer ([-output_size, 0)); its ring end lies ahead of it, within R.
-    // An exit state may also lie a little past its ring end: a walk that
-    // crossed own_hi inside a T2 scan whose next block leaves the ring (the
-    // state's next step is the refill, pos = ring_end, rx.cpp:137-145)
-    const long past = ofdm::WALK_SCAN_MAX + c->t2;
-    if (R > 0 ? (start < -flen0 || start_state.ring_end <= start - past || start_state.ring_end > start + R + flen0)
-              : start < 0)
-        return fail(OFDM_ERR_INVALID, "start state out of range (ring mode: -output_size <= pos, pos - %ld < ring_end "
-                                      "<= pos + R + output_size)", past);
-    if (own_lo < 0 || own_lo > own_hi || own_hi > (long)n)
-        return fail(OFDM_ERR_INVALID, "need 0 <= own_lo <= own_hi <= n");
-    if (c->t2_logn < 6 || c->t2_logn > 11) return fail(OFDM_ERR_UNSUPPORTED, "stream walk needs T2sin_size = 2^a, 64..2048");
-    if ((iq && !aligned16(iq)) || (iq16 && ((uintptr_t)iq16 & 3)) || (constell_out && !aligned16(constell_out)))
-        return fail(OFDM_ERR_INVALID, "misaligned buffer (complex<double> 16 B, complex<int16> 4 B)");
-    if (n > (size_t)1 << 40) return fail(OFDM_ERR_INVALID, "stream too long");
-    hipStream_t st = (hipStream_t)stream;
-    const long L = c->L, pre = (long)L * c->npr, msg = (long)L * c->S, span = pre + msg;
-    const long flen = c->geo.frame_len, nn = (long)n;
-    if (nn == 0 || start >= nn) return OFDM_OK;
-    // walkers: one chunk per resident walker slot by default, each >= 8 frames
-    const long slots = ofdm::stream_walk_slots(c->t2_logn, (int)c->p.pr_sin_len,
-                                               (int)(2 * c->p.t2sin_size + c->p.pr_sin_len), c->d_tspec != nullptr);
-    // Per-context tuning (ofdm_set_walk_tuning): chunks per walker slot,
-    // walk-in halo and walk-on extension in 1/1000 frames, look-back
-    // stitching. Look-back (the default): chunks start at their core (no
-    // walk-in) and each walks on past its core end until its walk joins the
-    // next chunk's (a device-side check of the records that chunk publishes);
-    // the chain of joined walks is the sequential walk, resolved on the
-    // device. Without it (lookback = 0, or the fallback when a walker's
-    // records overflow): each chunk walks in from a 3-frame halo and the host
-    // stitches the walks, re-walking a chunk whose walk-in did not meet the
-    // true walk.
-    const ofdm_walk_tuning& tu = c->walk;
-    const long qper = std::max(1L, tu.chunks_per_slot);
-    const long span_w = own_hi - own_lo;  // the chunk cores tile [own_lo, own_hi)
-    if (chunk <= 0) chunk = std::max(8 * flen, (span_w + slots * qper - 1) / (slots * qper));
-    chunk = std::max(chunk, (long)c->t2);
-    const long nchunks = std::max(1L, (span_w + chunk - 1) / chunk);
-    if (nchunks > 1 << 20) return fail(OFDM_ERR_INVALID, "chunk too small for this stream");
-    // look-back needs a resolvable chunk count and per-chunk record counts
-    // below 2^14 (the resolve kernel's packing): else the halo walk
-    bool lbk = tu.lookback && !force_halo && nchunks <= ofdm::RESOLVE_MAX_CHUNKS &&
-               (2 * chunk + std::max(0L, own_lo - start)) / msg < 8192;
-    const long halo = (tu.halo_milli < 0 ? (lbk ? 0L : 3000L) : tu.halo_milli) * flen / 1000;
-    const long ext = std::max(0L, tu.ext_milli) * flen / 1000;
-    // each located frame advances the walk by > message_len, and a walker can
-    // walk on past its core end by ext plus one scan step (WALK_SCAN_MAX
-    // samples) and the preamble window: this many records always suffice
-    // (chunk 0 walks in from `start`, the others a halo before their core).
-    // A look-back walker may walk on through the next core too (its walk met
-    // no record of that chunk's); one more overflows: the host falls back
-    int max_rec =
-        (int)(((lbk ? 2 : 1) * chunk + std::max(halo, own_lo - start) + std::max(ext, 2 * flen) + ofdm::WALK_SCAN_MAX +
-               2 * c->p.t2sin_size + c->p.pr_sin_len) / msg + (lbk ? 8 : 4));
-    // test hook: a smaller record buffer makes look-back walkers overflow
-    // (the halo walk, which the cap does not touch, then takes the call)
-    if (lbk && tu.max_rec_cap > 0) max_rec = std::min(max_rec, tu.max_rec_cap);
-    int rc;
-    const size_t rec_b = (size_t)nchunks * max_rec * sizeof(long);
-    // layout: records | exit states | exit ring ends | re-walk start (pos, ring end) | counts | ...
-    const size_t walk_b0 = rec_b + (size_t)nchunks * (2 * sizeof(long) + sizeof(int)) + 2 * sizeof(long) + 64;
-    const size_t walk_b = walk_b0 + 2 * (size_t)nchunks * sizeof(int);  // + in-core counts and first indices
-    const size_t link_b = 3 * (size_t)nchunks * sizeof(int);            // + look-back links
-    if ((rc = grow(c, c->s_walk, walk_b + link_b))) return rc;
-    char* wb = static_cast<char*>(c->s_walk.p);
-    long* d_rec = reinterpret_cast<long*>(wb);
-    long* d_exit = reinterpret_cast<long*>(wb + rec_b);
-    long* d_exit_ring = d_exit + nchunks;
-    long* d_start = d_exit_ring + nchunks;  // one re-walk start state (pos, ring end)
-    int* d_nrec = reinterpret_cast<int*>(d_start + 2);
-    int* d_ids = d_nrec + nchunks;     // one re-walk chunk id (in the 64 B slack)
-    int* d_ncore = reinterpret_cast<int*>(wb + walk_b0);
-    int* d_first_in = d_ncore + nchunks;
-    int* d_link = reinterpret_cast<int*>(wb + walk_b);
-
-    ofdm::WalkArgs w{};
-    w.exact_only = tu.exact_search != 0;
-    w.tw_m = c->d_twm;
-    w.tspec = c->d_tspec;  // nullptr: direct certified search
-    w.tspec_max = c->tspec_max;
-    w.tspec32 = tu.pre_f32 ? c->d_tspec32 : nullptr;  // FP32 tier of the FFT search
-    w.iq = reinterpret_cast<const double2*>(iq);
-    w.iq16 = reinterpret_cast<const short2*>(iq16);
-    w.n = nn;
-    w.t2tw = c->d_t2tw;
-    const int sm = (int)c->p.smooth, f1 = (int)c->p.t2_sin_f1, f2 = (int)c->p.t2_sin_f2;
-    w.a1 = std::max(0, f1 - sm);
-    w.b1 = std::min(c->t2 - 1, f1 + sm);
-    w.a2 = std::max(0, f2 - sm);
-    w.b2 = std::min(c->t2 - 1, f2 + sm);
-    w.t2_level = (double)c->p.t2_sin_level / 1000;
-    // FP32 T2 screen (certified, FP64 re-evaluation of uncertain steps)
-    w.t2_f32 = tu.t2_f32 != 0;
-    w.t2_margin = tu.t2_margin;
-    w.templ = c->d_templ;
-    w.L = (int)c->p.pr_sin_len;
-    w.cycles = (int)(2 * c->p.t2sin_size + c->p.pr_sin_len);
-    w.pr_level = (double)c->p.pr_level / 1000;
-    w.pre = pre;
-    w.msg = msg;
-    w.chunk = chunk;
-    w.halo = halo;
-    w.start = start;
-    w.ring = R;
-    w.out_len = flen;
-    w.start_ring_end = start_state.ring_end;
-    w.ring_phase = R > 0 ? ((start_state.ring_end % R) + R) % R : 0;
-    w.exit_ring = d_exit_ring;
-    w.core_lo = own_lo;
-    w.core_hi = own_hi;
-    w.ext = ext;
-    // A chunk whose core end falls inside a T2 scan (its last frame well
-    // before the end, e.g. a frame the reference's walk misses) walks on to
-    // the next frame it locates: the next chunk's walk locates that frame
-    // too, so the two sync without a serial re-walk (2048 chunks of config 4:
-    // one re-walk per call without this).
-    w.ext_scan = std::max(ext, 2 * flen);
-    w.max_rec = max_rec;
-    w.rec = d_rec;
-    w.nrec = d_nrec;
-    w.exit_pos = d_exit;
-    w.ncore = d_ncore;
-    w.first_in = d_first_in;
-    // the walkers take chunks from a queue: one resident round of workgroups
-    // drains it, slower walkers taking fewer chunks. The counter is zeroed by
-    // the previous call's compaction (stream order), else here.
-    if (!c->d_queue) {
-        HIP_TRY(hipMalloc((void**)&c->d_queue, 64));
-        c->queue_zero = false;
-    }
-    w.queue = c->d_queue;
-    w.nchunks = nchunks;
-    // The previous stream call's work must be done before this one rewrites
-    // the ctx's scratch (walk records, compacted list, channel): its decodes
-    // read them. On the same stream that is stream order; on another stream
-    // this call waits for an event recorded now on the previous call's stream
-    // (behind that call's decodes; header: overlapping stream calls take two
-    // contexts). Recorded here rather than at the end of every call: an event
-    // between two dependent kernels of one stream costs a launch gap (the
-    // next call's walker started ~15-25 us after the decode ended).
-    if (c->call_valid && c->call_stream != st) {
-        if (!c->ev_call) HIP_TRY(hipEventCreateWithFlags(&c->ev_call, hipEventDisableTiming));
-        if (hipEventRecord(c->ev_call, c->call_stream) == hipSuccess) {
-            HIP_TRY(hipStreamWaitEvent(st, c->ev_call, 0));
-        } else {
-            (void)hipGetLastError();  // that stream is gone (destroyed): wait for the device instead
-            HIP_TRY(hipDeviceSynchronize());
-        }
-    }
-    c->call_stream = st;
-    c->call_valid = true;
-    if (!c->queue_zero) HIP_TRY(hipMemsetAsync(w.queue, 0, sizeof(int), st));
-    c->queue_zero = false;
-    if (lbk) {
-        if (c->s_pub.bytes < (size_t)nchunks * sizeof(int)) {
-            if ((rc = grow(c, c->s_pub, (size_t)std::max(nchunks, 2048L) * sizeof(int)))) return rc;
-            c->pub_zero = false;
-        }
-        if (!c->pub_zero) HIP_TRY(hipMemsetAsync(c->s_pub.p, 0, c->s_pub.bytes, st));
-        c->pub_zero = false;  // until the resolve kernel clears it again
-        w.lookback = 1;
-        w.pub = static_cast<int*>(c->s_pub.p);
-        w.link = d_link;
-    }
-    // diagnostics: OFDM_WALK_PROF=<file> appends one JSON line per call with
-    // every chunk's walker timeline (WalkArgs::prof)
-    const char* prof_path = getenv("OFDM_WALK_PROF");
-    long* d_prof = nullptr;
-    if (prof_path) HIP_TRY(hipMalloc((void**)&d_prof, (size_t)nchunks * ofdm::WALK_PROF_FIELDS * sizeof(long)));
-    w.prof = d_prof;
-    c->phase_valid = false;
-    const bool timed = c->phase_timing && lbk;  // events between the kernels: measurement calls only
-    if (timed) HIP_TRY(hipEventRecord(c->ev_phase[0], st));
-    hipError_t e = ofdm::launch_stream_walk(c->t2_logn, w, std::min(nchunks, slots), st);
-    if (e != hipSuccess) return hip_fail(e, "stream_walk launch");
-    if (timed) HIP_TRY(hipEventRecord(c->ev_phase[1], st));
-    if (d_prof) {
-        std::vector<long> hp((size_t)nchunks * ofdm::WALK_PROF_FIELDS);
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipMemcpy(hp.data(), d_prof, hp.size() * sizeof(long), hipMemcpyDeviceToHost));
-        HIP_TRY(hipFree(d_prof));
-        if (FILE* f = fopen(prof_path, "a")) {
-            fprintf(f, "{\"nchunks\": %ld, \"chunk\": %ld, \"lookback\": %d, \"grid\": %ld, \"fields\": "
-                       "[\"t0\", \"t_core\", \"t_end\", \"ext_frames\", \"waits\", \"block\", \"xcc\", \"nrec\", "
-                       "\"t2_ticks\", \"pre_ticks\", \"scan_steps\", \"fp64_evals\", \"searches\", \"hw_id\"], "
-                       "\"chunks\": [", nchunks, chunk, (int)lbk, std::min(nchunks, slots));
-            for (long k = 0; k < nchunks; ++k) {
-                fprintf(f, "%s[", k ? "," : "");
-                for (int i = 0; i < ofdm::WALK_PROF_FIELDS; ++i)
-                    fprintf(f, "%s%ld", i ? "," : "", hp[(size_t)k * ofdm::WALK_PROF_FIELDS + i]);
-                fprintf(f, "]");
-            }
-            fprintf(f, "]}\n");
-            fclose(f);
-        }
-    }
-
-    // Fused decode: three kernels read each frame from the stream in place
-    // (pilot_freq_sinh; the other sync stages' parameters + chan_char_lq;
-    // rx with the corrections applied on load), no frame copy, no corrected
-    // copy. Needs the register-window rx and a pilot_freq_sinh plan.
-    ofdm_ctx::CfoPlan* pl = nullptr;
-    const bool fused = c->S <= ofdm::RX_SMAX && c->D <= ofdm::RX_DPT * (c->N / 8) && c->P <= c->N / 8 &&
-                       c->npr == 1 && c->S + 1 <= 64 && c->L % (c->N / 8) == 0 && c->L / (c->N / 8) <= 16 &&
-                       c->cp <= 2 * (c->N / 8) &&  // stream_params_kernel: CP template in 2 registers
-                       cfo_plan(c, c->npr, &pl, st) == OFDM_OK;
-    const size_t per = (size_t)c->D * sizeof(double2) + (size_t)c->S * ofdm::CORR_PER_SYM * sizeof(double2) + sizeof(double);
-    const long npts = (long)c->D * c->S;
-    // frames [0, nb) of d_list (device count d_cnt, if set, bounds them further)
-    auto decode_fused = [&](const long* d_list, size_t nb_total, const long* d_cnt) -> int {
-        const size_t bmax = std::max<size_t>(1, ((size_t)256 << 20) / per);
-        const size_t nb0 = std::min(nb_total, bmax);
-        int r2;
-        if ((r2 = grow(c, c->s_chan, nb0 * per))) return r2;
-        double2* chan = static_cast<double2*>(c->s_chan.p);
-        double2* corr = chan + nb0 * c->D;
-        double* cfo_tmp = reinterpret_cast<double*>(corr + nb0 * c->S * ofdm::CORR_PER_SYM);
-        for (size_t f0 = 0; f0 < nb_total; f0 += nb0) {
-            const size_t nb = std::min(nb0, nb_total - f0);
-            double* cfo = cfo_out ? cfo_out + f0 : cfo_tmp;
-            ofdm::CfoArgs ca{};
-            ca.x = reinterpret_cast<const double2*>(iq);
-            ca.x16 = reinterpret_cast<const short2*>(iq16);
-            ca.starts = d_list + f0;
-            ca.nframes = (long)nb;
-            ca.tw_sub = pl->tw_sub;
-            ca.tw_full = pl->tw_full;
-            ca.borders = pl->borders;
-            ca.P = c->P;
-            ca.cfo_out = cfo;
-            ca.count = d_cnt;  // single batch when set (f0 == 0)
-            ofdm::StreamParamsArgs sa{};
-            sa.tab = c->tables(true);
-            sa.iq = reinterpret_cast<const double2*>(iq);
-            sa.iq16 = reinterpret_cast<const short2*>(iq16);
-            sa.starts = d_list + f0;
-            sa.nframes = (long)nb;
-            sa.cfo = cfo;
-            sa.pre = c->d_preamble;
-            sa.mod_pre = c->d_modpre;
-            sa.chan_out = chan;  // internal scratch: reciprocals for rx's multiply
-            sa.chan_recip = true;
-            sa.corr_out = corr;
-            sa.npr = c->npr;
-            sa.S = c->S;
-            sa.D = c->D;
-            sa.P = c->P;
-            sa.cp = c->cp;
-            sa.pilot_ampl = (double)c->p.pilot_ampl / 1000;
-            sa.count = d_cnt;
-            ofdm::RxArgs ra{};
-            ra.tab = c->tables(false);
-            ra.iq = reinterpret_cast<const double2*>(iq);
-            ra.iq16 = reinterpret_cast<const short2*>(iq16);
-            ra.nframes = (long)nb;
-            ra.starts = d_list + f0;
-            ra.start_off = pre + c->cp;
-            ra.count = d_cnt;
-            ra.corr = corr;
-            ra.chan = chan;
-            ra.chan_stride = c->D;
-            ra.chan_recip = true;
-            ra.constell = constell_out ? reinterpret_cast<double2*>(constell_out) + f0 * npts : nullptr;
-            ra.bytes = bytes_out ? bytes_out + f0 * c->geo.bytes_per_frame : nullptr;
-            ra.S = c->S;
-            ra.D = c->D;
-            ra.P = c->P;
-            ra.seg = c->seg;
-            ra.cp = c->cp;
-            ra.k = c->k;
-            ra.bytes_per_frame = c->geo.bytes_per_frame;
-            ra.pilot_ampl = (double)c->p.pilot_ampl / 1000;
-            // static frame order: the next frame's symbol 0 is fetched ahead of
-            // the gains (stream rx 500 -> 416 us with the queue's late fetch)
-            ra.queue = nullptr;
-            // One kernel for the whole decode where the geometry allows (N =
-            // 512, 640-point CFO form: sync stage + rx stage per frame, the
-            // ramps and channel through LDS); else pilot_freq_sinh + the
-            // params stage (one kernel or two), then the stream rx.
-            hipError_t e2 = c->walk.staged_decode
-                                ? hipErrorNotSupported
-                                : ofdm::launch_stream_decode(ca, sa, ra, c->logn, pl->logm, pl->g, st);
-            if (e2 == hipErrorNotSupported) {
-                // other geometries: pilot_freq_sinh, the params stage, then
-                // the stream rx (two waves per frame at N = 512)
-                e2 = ofdm::launch_cfo(pl->logm, pl->g, ca, st);
-                if (e2 != hipSuccess) return hip_fail(e2, "stream cfo launch");
-                e2 = ofdm::launch_stream_params(c->logn, sa, st);
-                if (e2 != hipSuccess) return hip_fail(e2, "stream params launch");
-                e2 = ofdm::launch_rx(c->logn, ra, st, nullptr);
-                if (e2 != hipSuccess) return hip_fail(e2, "stream rx launch");
-            } else if (e2 != hipSuccess) {
-                return hip_fail(e2, "stream decode launch");
-            }
-        }
-        return OFDM_OK;
-    };
-    // Geometries the fused kernels do not take: gather each frame of d_list
-    // into a batch, then the staged sync chain + demod
-    auto decode_gathered = [&](const long* d_list, size_t nout) -> int {
-        const size_t fb = (size_t)span * sizeof(double2);
-        const size_t bmax = std::max<size_t>(1, std::min<size_t>(65535, ((size_t)256 << 20) / fb));
-        const size_t nb0 = std::min(nout, bmax);
-        int r2;
-        if ((r2 = grow(c, c->s_batch, nb0 * fb)) || (r2 = grow(c, c->s_chan, nb0 * c->D * sizeof(double2)))) return r2;
-        double* batch = static_cast<double*>(c->s_batch.p);
-        double* chan = static_cast<double*>(c->s_chan.p);
-        for (size_t f0 = 0; f0 < nout; f0 += nb0) {
-            const size_t nb = std::min(nb0, nout - f0);
-            ofdm::GatherArgs ga{reinterpret_cast<const double2*>(iq), reinterpret_cast<const short2*>(iq16), nn,
-                                d_list + f0, (long)nb, span, reinterpret_cast<double2*>(batch)};
-            hipError_t e2 = ofdm::launch_gather(ga, st);
-            if (e2 != hipSuccess) return hip_fail(e2, "gather launch");
-            if ((r2 = ofdm_sync_frames(c, batch, nb, (size_t)span, OFDM_SYNC_ALL, nullptr,
-                                       cfo_out ? cfo_out + f0 : nullptr, chan, stream)))
-                return r2;
-            if ((r2 = ofdm_rx_demod(c, batch + 2 * pre, nb, (size_t)span, chan, (size_t)c->D,
-                                    constell_out ? constell_out + 2 * f0 * npts : nullptr,
-                                    bytes_out ? bytes_out + f0 * c->geo.bytes_per_frame : nullptr, nullptr, nullptr,
-                                    stream)))
-                return r2;
-        }
-        return OFDM_OK;
-    };
-
-    if (lbk) {
-        // The true walk, resolved on the device: the owned frames straight
-        // into the decode's list (and pb_out), a status block to the host.
-        // The decode is enqueued behind it before the host reads the status.
-        const size_t ub = std::min(max_frames, (size_t)nchunks * max_rec);
-        const bool want_chain = (located || located_lag) && located_cap > 0;
-        const size_t chain_tail = located_cap / 2, chain_head = located_cap - chain_tail;
-        if ((rc = grow(c, c->s_pbs, (ub + 1) * sizeof(long))) || (rc = grow_host(c, c->h_status, 64)) ||
-            (want_chain && (rc = grow(c, c->s_chain, located_cap * sizeof(long)))))
-            return rc;
-        long* d_pbs = static_cast<long*>(c->s_pbs.p);
-        volatile long* hs = static_cast<volatile long*>(c->h_status.p);
-        hs[1] = -1;  // overwritten by the resolve kernel
-        ofdm::ResolveArgs ra{};
-        ra.rec = d_rec;
-        ra.nrec = d_nrec;
-        ra.link = d_link;
-        ra.exit_pos = d_exit;
-        ra.exit_ring = d_exit_ring;
-        ra.nchunks = nchunks;
-        ra.max_rec = max_rec;
-        // a core starting at the stream's first sample also owns a frame whose
-        // preamble starts before it (rx.cpp:105-114,158: its zero header)
-        ra.own_lo = own_lo == 0 ? LONG_MIN : own_lo;
-        ra.own_hi = own_hi;
-        ra.cap = (long)ub;
-        ra.list = d_pbs;
-        ra.list2 = pb_out;
-        ra.count = d_pbs + ub;
-        ra.chain = want_chain ? static_cast<long*>(c->s_chain.p) : nullptr;
-        ra.chain_head = (long)chain_head;
-        ra.chain_tail = (long)chain_tail;
-        ra.status = const_cast<long*>(hs);
-        ra.pub = w.pub;
-        ra.queue_reset = c->d_queue;
-        e = ofdm::launch_resolve(ra, st);
-        if (e != hipSuccess) return hip_fail(e, "stream resolve launch");
-        c->pub_zero = true;    // cleared by the resolve (stream order)
-        c->queue_zero = true;  // likewise the chunk counter
-        if (timed) HIP_TRY(hipEventRecord(c->ev_phase[2], st));
-        const bool spec = fused && ub > 0 && ub * per <= ((size_t)256 << 20);
-        if (spec && (rc = decode_fused(d_pbs, ub, d_pbs + ub))) return rc;
-        if (timed && spec) {
-            HIP_TRY(hipEventRecord(c->ev_phase[3], st));
-            c->phase_valid = true;
-        }
-        // the resolve kernel's last word is the flags word of the status:
-        // poll it (no event between the resolve and the decode: a marker
-        // between two dependent kernels costs a launch gap); if it has not
-        // landed in 2 s, wait for the stream (errors surface there)
-        {
-            const auto t0 = std::chrono::steady_clock::now();
-            for (long spin = 0; hs[1] == -1; ++spin)
-                if ((spin & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
-                    HIP_TRY(hipStreamSynchronize(st));
-                    break;
-                }
-        }
-        const long owned = hs[0], flags = hs[1], xpos = hs[2], xring = hs[3], nchain = hs[4], nneg = hs[5];
-        if (flags < 0) return fail(OFDM_ERR_HIP, "stream resolve wrote no status");
-        if (flags & ofdm::RESOLVE_OVERFLOW) {
-            // a walker's records overflowed (a walk that met no later chunk's
-            // through a whole core): the halo walk with host stitching
-            if (getenv("OFDM_STREAM_DEBUG")) fprintf(stderr, "ofdm_rx_stream: look-back overflow, halo walk\n");
-            return rx_stream_impl(c, iq, iq16, n, max_frames, chunk, pb_out, bytes_out, constell_out, cfo_out,
-                                  nframes_out, stream, start_state, own_lo, own_hi, located, located_lag, located_cap,
-                                  nlocated_out, exit_out, true);
-        }
-        *nframes_out = (size_t)owned;
-        if (exit_out) *exit_out = ofdm_walk_state{xpos, xpos < 0 ? 0 : xring};
-        if (nlocated_out) *nlocated_out = (size_t)nchain;
-        if (want_chain) {
-            const size_t nl = std::min((size_t)nchain, located_cap);
-            if (nl) {
-                std::vector<long> rl(nl);
-                HIP_TRY(hipMemcpy(rl.data(), c->s_chain.p, nl * sizeof(long), hipMemcpyDeviceToHost));
-                for (size_t i = 0; i < nl; ++i) {
-                    const long r = rl[i];
-                    if (located) located[i] = r < 0 ? r : (r & ofdm::WALK_REC_PB);
-                    if (located_lag) located_lag[i] = r > 0 && (r & ofdm::WALK_REC_LAG) ? 1 : 0;
-                }
-            }
-        }
-        if (getenv("OFDM_STREAM_DEBUG"))
-            fprintf(stderr, "ofdm_rx_stream: look-back, %ld chunks of %ld samples, halo %ld, %ld frames\n", nchunks,
-                    chunk, halo, owned);
-        const size_t nout = std::min((size_t)owned, ub);
-        // frames before sample 0 (a prefix; the fused kernels skip them): the
-        // gather path, whose samples before 0 read as zero like rx.cpp's header
-        const size_t neg = (flags & ofdm::RESOLVE_NEG_FRAME) ? std::min((size_t)nneg, nout) : 0;
-        if (spec) return neg ? decode_gathered(d_pbs, neg) : OFDM_OK;
-        if (nout == 0) return OFDM_OK;
-        if (!fused) return decode_gathered(d_pbs, nout);
-        if ((rc = decode_fused(d_pbs, nout, nullptr))) return rc;
-        return neg ? decode_gathered(d_pbs, neg) : OFDM_OK;
-    }
-
-    // records, exit states and counts in one copy of the walk buffer's layout
-    if ((rc = grow_host(c, c->h_walk, walk_b))) return rc;
-    char* hb = static_cast<char*>(c->h_walk.p);
-    long* rec = reinterpret_cast<long*>(hb);
-    long* ex = reinterpret_cast<long*>(hb + rec_b);
-    long* exr = ex + nchunks;
-    int* nrec = reinterpret_cast<int*>(exr + nchunks + 2);
-    if (!c->ev_walk) HIP_TRY(hipEventCreateWithFlags(&c->ev_walk, hipEventDisableTiming));
-    if (!c->ev_wdone) HIP_TRY(hipEventCreateWithFlags(&c->ev_wdone, hipEventDisableTiming));
-    if (!c->side) HIP_TRY(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
-    // Speculative decode: every chunk's in-core records, compacted on the
-    // device behind the walk, are decoded while the host stitches the walks.
-    // That list is the stitched walk unless a chunk needs a re-walk (or the
-    // walk ends early); then the host's list is decoded again over it.
-    const size_t ub = std::min(max_frames, (size_t)nchunks * max_rec);
-    const bool spec = fused && ub > 0 && ub * per <= ((size_t)256 << 20);
-    long* d_pbs = nullptr;
-    if (spec) {
-        if ((rc = grow(c, c->s_pbs, (ub + 1) * sizeof(long)))) return rc;
-        d_pbs = static_cast<long*>(c->s_pbs.p);
-        ofdm::CompactArgs ka{};
-        ka.rec = d_rec;
-        ka.ncore = d_ncore;
-        ka.first_in = d_first_in;
-        ka.nchunks = nchunks;
-        ka.max_rec = max_rec;
-        ka.cap = (long)ub;
-        ka.list = d_pbs;
-        ka.list2 = pb_out;
-        ka.count = d_pbs + ub;
-        ka.queue_reset = c->d_queue;  // after the walk (stream order): zero for the next call
-        e = ofdm::launch_compact(ka, st);
-        if (e != hipSuccess) return hip_fail(e, "stream compact launch");
-    }
-    // The walk records go to the host on a side stream, so the decode on the
-    // caller's stream does not queue behind the copy. The one event marks the
-    // walk and the compaction together: a marker between two dependent
-    // kernels costs a launch gap, so walk -> compaction runs back to back.
-    HIP_TRY(hipEventRecord(c->ev_wdone, st));
-    HIP_TRY(hipStreamWaitEvent(c->side, c->ev_wdone, 0));
-    HIP_TRY(hipMemcpyAsync(hb, wb, walk_b, hipMemcpyDeviceToHost, c->side));
-    HIP_TRY(hipEventRecord(c->ev_walk, c->side));
-    if (spec) {
-        if ((rc = decode_fused(d_pbs, ub, d_pbs + ub))) return rc;
-        // the queue counter was zeroed by the compaction (stream order)
-        c->queue_zero = true;
-    }
-    HIP_TRY(hipEventSynchronize(c->ev_walk));
-
-    // the speculative list, from the walks as they came back
-    // a record's preamble start (ring mode: the lag bit stripped; a frame
-    // before the stream's first sample stays negative)
-    auto rec_pb = [](long r) { return r < 0 ? r : (r & ofdm::WALK_REC_PB); };
-    std::vector<long> spec_list;
-    if (spec)
-        for (long k = 0; k < nchunks; ++k) {
-            const long lo = own_lo + k * chunk, hi = std::min(lo + chunk, own_hi);
-            for (int i = 0; i < std::min(nrec[k], max_rec); ++i) {
-                const long pb = rec_pb(rec[(size_t)k * max_rec + i]);
-                if (pb >= lo && pb < hi) spec_list.push_back(pb);
-            }
-        }
-
-    // Stitch the chunk walks into the one true walk. Chunk 0 starts at the
-    // true initial state. Chunk k is accepted when its walk and the accepted
-    // walk before it locate a common frame no later than k's first owned
-    // frame (from there on both are the same computation); otherwise it is
-    // re-walked from the previous exit state (exact), with one workgroup.
-    long nrewalk = 0;
-    auto rewalk = [&](long k, long start, long start_ring) -> int {
-        ofdm::WalkArgs r = w;
-        const int id = (int)k;
-        const long st2[2] = {start, start_ring};
-        HIP_TRY(hipMemcpyAsync(d_start, st2, sizeof(st2), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_ids, &id, sizeof(int), hipMemcpyHostToDevice, st));
-        r.start_pos = d_start;
-        r.start_ring = d_start + 1;
-        r.chunk_ids = d_ids;
-        r.queue = nullptr;
-        ++nrewalk;
-        hipError_t e2 = ofdm::launch_stream_walk(c->t2_logn, r, 1, st);
-        if (e2 != hipSuccess) return hip_fail(e2, "stream_walk re-walk launch");
-        HIP_TRY(hipMemcpyAsync(rec + (size_t)k * max_rec, d_rec + (size_t)k * max_rec, max_rec * sizeof(long),
-                               hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(&ex[k], d_exit + k, sizeof(long), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(&exr[k], d_exit_ring + k, sizeof(long), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(&nrec[k], d_nrec + k, sizeof(int), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        return OFDM_OK;
-    };
-    // records compare whole (preamble start and, in ring mode, the ring of the
-    // state after the frame): equal records = equal walks from there on
-    std::vector<long> frames, walk_in;  // frames: preamble starts; walk_in: records
-    std::vector<long> owned_rec;        // the owned frames' records
-    std::vector<long> prev;  // every record of the accepted walk of the previous chunk
-    long texit = 0, texit_ring = start_state.ring_end, last_k = -1;
-    for (long k = 0; k < nchunks; ++k) {
-        if (k > 0 && texit < 0) break;  // the true walk ended
-        if (nrec[k] > max_rec) return fail(OFDM_ERR_HIP, "stream walk record overflow");
-        std::vector<long> lst(rec + (size_t)k * max_rec, rec + (size_t)k * max_rec + nrec[k]);
-        const long lo = own_lo + k * chunk, hi = std::min(lo + chunk, own_hi);
-        if (k > 0) {
-            long first_owned = LONG_MAX;
-            for (long r : lst)
-                if (rec_pb(r) >= lo && rec_pb(r) < hi) first_owned = std::min(first_owned, rec_pb(r));
-            bool sync = false;
-            for (long r : lst)
-                if (rec_pb(r) <= first_owned && std::find(prev.begin(), prev.end(), r) != prev.end()) sync = true;
-            if (!sync) {
-                if (getenv("OFDM_STREAM_DEBUG")) {
-                    fprintf(stderr, "ofdm_rx_stream: re-walk chunk %ld [%ld, %ld) from (%ld, %ld); its walk:", k, lo, hi,
-                            texit, texit_ring);
-                    for (long r : lst) fprintf(stderr, " %ld%s", rec_pb(r), r > 0 && (r & ofdm::WALK_REC_LAG) ? "+" : "");
-                    fprintf(stderr, " | previous:");
-                    for (long r : prev) fprintf(stderr, " %ld%s", rec_pb(r), r > 0 && (r & ofdm::WALK_REC_LAG) ? "+" : "");
-                    fprintf(stderr, "\n");
-                }
-                if ((rc = rewalk(k, texit, texit_ring))) return rc;
-                if (nrec[k] > max_rec) return fail(OFDM_ERR_HIP, "stream walk record overflow");
-                lst.assign(rec + (size_t)k * max_rec, rec + (size_t)k * max_rec + nrec[k]);
-            }
-        }
-        if (k == 0)  // the walk-in from `start` (true by definition): frames before own_lo; a
-            for (long r : lst) {  // core from sample 0 owns a frame before it (rx.cpp's zero header)
-                if (rec_pb(r) < lo && !(own_lo == 0 && r < 0)) walk_in.push_back(r);
-                if (own_lo == 0 && r < 0) {
-                    frames.push_back(r);
-                    owned_rec.push_back(r);
-                }
-            }
-        for (long r : lst)
-            if (rec_pb(r) >= lo && rec_pb(r) < hi) {
-                frames.push_back(rec_pb(r));
-                owned_rec.push_back(r);
-            }
-        prev.swap(lst);
-        texit = ex[k];
-        texit_ring = exr[k];
-        last_k = k;
-    }
-    *nframes_out = frames.size();
-    if (exit_out && last_k == nchunks - 1) *exit_out = ofdm_walk_state{texit, texit < 0 ? 0 : texit_ring};
-    if (nlocated_out) {
-        // every frame of the stitched walk: the walk-in, the owned frames, and
-        // what the last walker located past own_hi before it stopped
-        std::vector<long> all(walk_in);
-        all.insert(all.end(), owned_rec.begin(), owned_rec.end());
-        if (last_k == nchunks - 1)
-            for (long r : prev)
-                if (rec_pb(r) >= own_hi) all.push_back(r);
-        *nlocated_out = all.size();
-        // more than located_cap: the first located_cap - located_cap/2 and the last located_cap/2
-        if (all.size() > located_cap) {
-            const size_t tail = located_cap / 2, head = located_cap - tail;
-            std::vector<long> ht(all.begin(), all.begin() + head);
-            ht.insert(ht.end(), all.end() - tail, all.end());
-            all.swap(ht);
-        }
-        for (size_t i = 0; i < all.size(); ++i) {
-            if (located) located[i] = rec_pb(all[i]);
-            if (located_lag) located_lag[i] = all[i] > 0 && (all[i] & ofdm::WALK_REC_LAG) ? 1 : 0;
-        }
-    }
-    if (getenv("OFDM_STREAM_DEBUG"))
-        fprintf(stderr, "ofdm_rx_stream: %ld chunks of %ld samples, halo %ld, %ld re-walks, %zu frames, speculative %s\n",
-                nchunks, chunk, halo, nrewalk, frames.size(), spec ? (frames == spec_list ? "hit" : "miss") : "off");
-    const size_t nout = std::min(frames.size(), max_frames);
-    if (spec && frames == spec_list) return OFDM_OK;  // the speculative decode was the true one
-    if (nout == 0) return OFDM_OK;
-
-    // located frames -> main.cpp:60-80 chain + demod
-    if ((rc = grow(c, c->s_pbs, (std::max(nout, ub) + 1) * sizeof(long))) ||
-        (rc = grow_host(c, c->h_frames, nout * sizeof(long))))
-        return rc;
-    d_pbs = static_cast<long*>(c->s_pbs.p);
-    // the previous call's copy out of the pinned stage must have finished: on
-    // the same stream the walk-record sync above saw to it
-    if (c->h_frames_used && c->h_frames_stream != st) HIP_TRY(hipStreamSynchronize(c->h_frames_stream));
-    c->h_frames_stream = st;
-    c->h_frames_used = true;
-    std::memcpy(c->h_frames.p, frames.data(), nout * sizeof(long));
-    HIP_TRY(hipMemcpyAsync(d_pbs, c->h_frames.p, nout * sizeof(long), hipMemcpyHostToDevice, st));
-    if (pb_out) HIP_TRY(hipMemcpyAsync(pb_out, d_pbs, nout * sizeof(long), hipMemcpyDeviceToDevice, st));
-
-    if (!fused) return decode_gathered(d_pbs, nout);
-    if ((rc = decode_fused(d_pbs, nout, nullptr))) return rc;
-    size_t neg = 0;  // frames before sample 0: the gather path (the fused kernels skip them)
-    while (neg < nout && frames[neg] < 0) ++neg;
-    return neg ? decode_gathered(d_pbs, neg) : OFDM_OK;
-}
-
-extern "C" {
-
+// The stream receiver (ofdm_stream_call.cpp). ofdm_rx_stream / _i16: the whole
+// stream from rx.cpp's initial state, no shard report.
 int ofdm_rx_stream(ofdm_ctx* c, const double* iq, size_t n, size_t max_frames, long chunk, long* pb_out,
                    uint8_t* bytes_out, double* constell_out, double* cfo_out, size_t* nframes_out, void* stream)
 {
-    if (!iq) return fail(OFDM_ERR_INVALID, "null argument");
-    return rx_stream_impl(c, iq, nullptr, n, max_frames, chunk, pb_out, bytes_out, constell_out, cfo_out,
-                          nframes_out, stream, initial_state(c), 0, (long)n, nullptr, nullptr, 0, nullptr, nullptr);
+    if (!c || !iq) return fail(OFDM_ERR_INVALID, "null argument");
+    const ofdm::StreamCall a{iq, nullptr, n, max_frames, chunk, pb_out, bytes_out, constell_out, cfo_out, nframes_out,
+                             stream, initial_state(c), 0, (long)n, nullptr, nullptr, 0, nullptr, nullptr};
+    return ofdm::rx_stream_call(c, a);
 }
 
 int ofdm_rx_stream_i16(ofdm_ctx* c, const int16_t* iq16, size_t n, size_t max_frames, long chunk, long* pb_out,
                        uint8_t* bytes_out, double* constell_out, double* cfo_out, size_t* nframes_out, void* stream)
 {
-    if (!iq16) return fail(OFDM_ERR_INVALID, "null argument");
-    return rx_stream_impl(c, nullptr, iq16, n, max_frames, chunk, pb_out, bytes_out, constell_out, cfo_out,
-                          nframes_out, stream, initial_state(c), 0, (long)n, nullptr, nullptr, 0, nullptr, nullptr);
+    if (!c || !iq16) return fail(OFDM_ERR_INVALID, "null argument");
+    const ofdm::StreamCall a{nullptr, iq16, n, max_frames, chunk, pb_out, bytes_out, constell_out, cfo_out, nframes_out,
+                             stream, initial_state(c), 0, (long)n, nullptr, nullptr, 0, nullptr, nullptr};
+    return ofdm::rx_stream_call(c, a);
 }
 
 int ofdm_stream_shard_margins(const ofdm_ctx* c, long* halo_out, long* tail_out)
@@ -2447,8 +1702,9 @@ int ofdm_rx_stream_shard(ofdm_ctx* c, const double* iq, const int16_t* iq16, siz
 {
     if (!iq == !iq16) return fail(OFDM_ERR_INVALID, "exactly one of iq, iq16");
     if (!c || !start) return fail(OFDM_ERR_INVALID, "null argument");
-    return rx_stream_impl(c, iq, iq16, n, max_frames, chunk, pb_out, bytes_out, constell_out, cfo_out, nframes_out,
-                          stream, *start, own_lo, own_hi, located, located_lag, located_cap, nlocated_out, exit_out);
+    const ofdm::StreamCall a{iq, iq16, n, max_frames, chunk, pb_out, bytes_out, constell_out, cfo_out, nframes_out,
+                             stream, *start, own_lo, own_hi, located, located_lag, located_cap, nlocated_out, exit_out};
+    return ofdm::rx_stream_call(c, a);
 }
 
 int ofdm_set_stream_timing(ofdm_ctx* c, int on)

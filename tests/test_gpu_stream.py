@@ -658,3 +658,50 @@ def test_channel_stream_gathered_decode_chan_kernel():
     gathered and take the staged sync chain, whose chan_kernel<9> runs
     unwrap_scan<64> on the gathered batch."""
     _check_channel_stream("stream-D_s12-three", 20000)
+
+
+def _shard_whole_stream(m, dx, n, located_cap, chunk, max_frames=256):
+    """ofdm_rx_stream_shard over the whole stream (start = the initial state,
+    own [0, n)), called on the C-ABI so that nlocated comes back too."""
+    g = O.geometry(D)
+    pbs = torch.full((max_frames,), -1, dtype=torch.int64, device="cuda")
+    out = torch.zeros((max_frames * g["bytes_per_frame"],), dtype=torch.uint8, device="cuda")
+    cons = torch.zeros((max_frames * g["npts"],), dtype=torch.complex128, device="cuda")
+    cfo = torch.zeros((max_frames,), dtype=torch.float64, device="cuda")
+    loc = np.full(max(1, located_cap), -7, np.int64)
+    lag = np.full(max(1, located_cap), 7, np.uint8)
+    st, ex = M.WalkState(*m.initial_state()), M.WalkState()
+    nf, nl = C.c_size_t(), C.c_size_t()
+    M.check(M.lib().ofdm_rx_stream_shard(m.h, dx.data_ptr(), None, n, C.byref(st), 0, n, max_frames, chunk,
+                                         pbs.data_ptr(), out.data_ptr(), cons.data_ptr(), cfo.data_ptr(),
+                                         C.byref(nf), loc.ctypes.data, lag.ctypes.data, located_cap, C.byref(nl),
+                                         C.byref(ex), None))
+    k = min(nl.value, located_cap)
+    return dict(nf=nf.value, nlocated=nl.value, loc=loc[:k], lag=lag[:k], exit=(ex.pos, ex.ring_end),
+                pbs=host(pbs), out=host(out), cons=host(cons), cfo=host(cfo))
+
+
+@pytest.mark.parametrize("ring", [None, 0], ids=["ring", "continuous"])
+@pytest.mark.parametrize("lookback", [1, 0], ids=["lookback", "host_stitch"])
+def test_stream_shard_located_list_truncation(lookback, ring):
+    """located_cap below the located count: the list holds the first
+    cap - cap/2 and the last cap/2 records of the full list (the resolve
+    kernel's chain_head / chain_tail with look-back, the host's located list
+    without), nlocated is the untruncated count, and nothing decoded changes."""
+    x, data = impaired_stream(D, 40, seed=4)
+    m = modem(D)
+    old_t, old_r = m.walk_tuning(lookback=lookback), m.stream_ring(ring)
+    try:
+        dx = dev(x)
+        full = _shard_whole_stream(m, dx, len(x), 4096, 9000)
+        cut = _shard_whole_stream(m, dx, len(x), 7, 9000)
+    finally:
+        m.walk_tuning(**old_t)
+        m.stream_ring(old_r)
+    assert full["nlocated"] == len(full["loc"]) > 7  # the cap of 7 truncates
+    assert cut["nlocated"] == full["nlocated"]
+    assert np.array_equal(cut["loc"], np.concatenate([full["loc"][:4], full["loc"][-3:]]))
+    assert np.array_equal(cut["lag"], np.concatenate([full["lag"][:4], full["lag"][-3:]]))
+    assert cut["nf"] == full["nf"] > 0 and cut["exit"] == full["exit"]
+    for key in ("pbs", "out", "cons", "cfo"):
+        assert np.array_equal(cut[key], full[key]), key

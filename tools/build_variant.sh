@@ -16,7 +16,10 @@ pids=()
 for f in $SRC/c-ofdm_amd/csrc/*.hip; do
   $H -c $f -o $B/$(basename $f .hip).o & pids+=($!)
 done
-$H -x hip -c $SRC/c-ofdm_amd/csrc/ofdm_capi.cpp -o $B/ofdm_capi.o & pids+=($!)
+# and every host source (ofdm_capi.cpp alone in older trees)
+for f in $SRC/c-ofdm_amd/csrc/*.cpp; do
+  $H -x hip -c $f -o $B/$(basename $f .cpp).o & pids+=($!)
+done
 for p in "${pids[@]}"; do wait $p; done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o $R/abtest/libofdm_$NAME.so $B/*.o -ldl
 rm -rf $B
