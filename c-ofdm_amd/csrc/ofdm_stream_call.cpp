@@ -30,6 +30,27 @@ constexpr size_t DECODE_BATCH_BYTES = (size_t)256 << 20;
 // OFDM_STREAM_DEBUG: one stderr line per call on how it went (asked once per call)
 bool stream_debug() { return getenv("OFDM_STREAM_DEBUG") != nullptr; }
 
+// OFDM_DECODE_BATCH_FRAMES=<n>, n >= 1 (test only, asked once per call): at
+// most n frames per decode launch, so that a short stream takes the batched,
+// non-speculative decode of a capture whose scratch passes DECODE_BATCH_BYTES.
+// A value that is not an integer >= 1 is ignored. Returns 0 for "no cap"
+size_t decode_batch_cap()
+{
+    const char* s = getenv("OFDM_DECODE_BATCH_FRAMES");
+    if (!s || !*s) return 0;
+    char* end = nullptr;
+    const long long v = strtoll(s, &end, 10);
+    return (*end == 0 && v >= 1) ? (size_t)v : 0;
+}
+
+// Frames per decode launch for `per` bytes of scratch per frame: what fits
+// DECODE_BATCH_BYTES (at least one), capped by the test hook
+size_t batch_frames(size_t per, size_t cap)
+{
+    const size_t n = std::max<size_t>(1, DECODE_BATCH_BYTES / per);
+    return cap ? std::min(n, cap) : n;
+}
+
 long preamble_len(const ofdm_ctx* c) { return (long)c->L * c->npr; }
 long message_len(const ofdm_ctx* c) { return (long)c->L * c->S; }
 
@@ -265,8 +286,10 @@ int order_after_previous_call(ofdm_ctx* c, hipStream_t st)
     return OFDM_OK;
 }
 
-// diagnostics: OFDM_WALK_PROF=<file> appends one JSON line per call with
-// every chunk's walker timeline (WalkArgs::prof)
+// diagnostics: OFDM_WALK_PROF=<file> appends one JSON line per walk launch
+// (a look-back walk that overflows and its halo walk: two; a re-walk: none)
+// with every chunk's walker timeline (WalkArgs::prof). T2sin_size = 256 only
+// (stream_walk_has_prof): other sizes have no diagnostics walker, no line
 int dump_walk_prof(const char* path, const long* d_prof, const WalkPlan& p, hipStream_t st)
 {
     std::vector<long> hp((size_t)p.nchunks * WALK_PROF_FIELDS);
@@ -319,7 +342,9 @@ int launch_walk(ofdm_ctx* c, Walk& wk, hipStream_t st)
         w.pub = static_cast<int*>(c->s_pub.p);
         w.link = wk.dev.link;
     }
-    const char* prof_path = getenv("OFDM_WALK_PROF");
+    // only the T2 size with a diagnostics walker writes a timeline; any other
+    // runs the normal walk and adds no line
+    const char* prof_path = stream_walk_has_prof(c->t2_logn) ? getenv("OFDM_WALK_PROF") : nullptr;
     long* d_prof = nullptr;
     if (prof_path) HIP_TRY(hipMalloc((void**)&d_prof, (size_t)nchunks * WALK_PROF_FIELDS * sizeof(long)));
     w.prof = d_prof;
@@ -343,6 +368,7 @@ struct Decode {
     ofdm_ctx::CfoPlan* pl;  // pilot_freq_sinh plan of the preamble form (fused)
     bool fused;             // the fused kernels take this geometry
     size_t per;             // their scratch per frame: channel, ramps, CFO
+    size_t batch_cap;       // OFDM_DECODE_BATCH_FRAMES (0: none)
     long npts;              // constellation points per frame
 };
 
@@ -358,9 +384,9 @@ bool fused_geometry(ofdm_ctx* c, hipStream_t st, ofdm_ctx::CfoPlan** pl)
            cfo_plan(c, c->npr, pl, st) == OFDM_OK;
 }
 
-Decode decode_backend(ofdm_ctx* c, const StreamCall& a, hipStream_t st)
+Decode decode_backend(ofdm_ctx* c, const StreamCall& a, hipStream_t st, size_t batch_cap)
 {
-    Decode d{c, &a, st, nullptr, false, 0, 0};
+    Decode d{c, &a, st, nullptr, false, 0, batch_cap, 0};
     d.fused = fused_geometry(c, st, &d.pl);
     d.per = (size_t)c->D * sizeof(double2) + (size_t)c->S * CORR_PER_SYM * sizeof(double2) + sizeof(double);
     d.npts = (long)c->D * c->S;
@@ -370,7 +396,7 @@ Decode decode_backend(ofdm_ctx* c, const StreamCall& a, hipStream_t st)
 // Whether up to `ub` frames may be decoded behind the walk before the host
 // knows the list: the fused kernels (they bound the list by a device count),
 // in one batch
-bool speculative_ok(const Decode& d, size_t ub) { return d.fused && ub > 0 && ub * d.per <= DECODE_BATCH_BYTES; }
+bool speculative_ok(const Decode& d, size_t ub) { return d.fused && ub > 0 && ub <= batch_frames(d.per, d.batch_cap); }
 
 // frames [0, nb_total) of d_list (device count d_cnt, if set, bounds them further)
 int decode_fused(const Decode& d, const long* d_list, size_t nb_total, const long* d_cnt)
@@ -378,7 +404,7 @@ int decode_fused(const Decode& d, const long* d_list, size_t nb_total, const lon
     ofdm_ctx* c = d.c;
     const StreamCall& a = *d.a;
     const ofdm_ctx::CfoPlan* pl = d.pl;
-    const size_t bmax = std::max<size_t>(1, DECODE_BATCH_BYTES / d.per);
+    const size_t bmax = batch_frames(d.per, d.batch_cap);
     const size_t nb0 = std::min(nb_total, bmax);
     int r2;
     if ((r2 = grow(c, c->s_chan, nb0 * d.per))) return r2;
@@ -474,7 +500,7 @@ int decode_gathered(const Decode& d, const long* d_list, size_t nout)
     const StreamCall& a = *d.a;
     const long pre = preamble_len(c), span = pre + message_len(c);
     const size_t fb = (size_t)span * sizeof(double2);
-    const size_t bmax = std::max<size_t>(1, std::min<size_t>(65535, DECODE_BATCH_BYTES / fb));
+    const size_t bmax = std::min<size_t>(65535, batch_frames(fb, d.batch_cap));
     const size_t nb0 = std::min(nout, bmax);
     int r2;
     if ((r2 = grow(c, c->s_batch, nb0 * fb)) || (r2 = grow(c, c->s_chan, nb0 * c->D * sizeof(double2)))) return r2;
@@ -777,7 +803,7 @@ int finish_halo(ofdm_ctx* c, const StreamCall& a, const Walk& wk, const Decode& 
 
 // One attempt at the call under `plan`: scratch, ordering, the walk, and the
 // plan's finish
-int run_walk(ofdm_ctx* c, const StreamCall& a, const WalkPlan& plan, bool debug, bool* overflow)
+int run_walk(ofdm_ctx* c, const StreamCall& a, const WalkPlan& plan, bool debug, size_t batch_cap, bool* overflow)
 {
     hipStream_t st = (hipStream_t)a.stream;
     Walk wk(plan);
@@ -787,7 +813,7 @@ int run_walk(ofdm_ctx* c, const StreamCall& a, const WalkPlan& plan, bool debug,
     if ((rc = fill_walk_args(c, a, plan, wk.dev, wk.args)) || (rc = order_after_previous_call(c, st)) ||
         (rc = launch_walk(c, wk, st)))
         return rc;
-    const Decode dec = decode_backend(c, a, st);
+    const Decode dec = decode_backend(c, a, st, batch_cap);
     return plan.lbk ? finish_lookback(c, a, wk, dec, debug, overflow) : finish_halo(c, a, wk, dec, debug);
 }
 
@@ -799,14 +825,16 @@ int rx_stream_call(ofdm_ctx* c, const StreamCall& a)
     if (rc) return rc;
     if (a.n == 0 || a.start.pos >= (long)a.n) return OFDM_OK;
     const bool debug = stream_debug();
+    const size_t batch_cap = decode_batch_cap();
     WalkPlan plan;
     bool overflow = false;
-    if ((rc = plan_walk(c, a, a.chunk, false, &plan)) || (rc = run_walk(c, a, plan, debug, &overflow))) return rc;
+    if ((rc = plan_walk(c, a, a.chunk, false, &plan)) || (rc = run_walk(c, a, plan, debug, batch_cap, &overflow)))
+        return rc;
     if (!overflow) return OFDM_OK;
     // a look-back walker's records overflowed: the whole call again as the
     // halo walk, over the same chunks
     if ((rc = plan_walk(c, a, plan.chunk, true, &plan))) return rc;
-    return run_walk(c, a, plan, debug, &overflow);
+    return run_walk(c, a, plan, debug, batch_cap, &overflow);
 }
 
 }  // namespace ofdm

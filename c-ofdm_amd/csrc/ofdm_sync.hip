@@ -2804,13 +2804,18 @@ static size_t walk_shm(int L, int C, bool fft)
     return WalkLds<LOGT>::FIXED + WalkLds<LOGT>::big(L, C, fft);
 }
 
+// the one T2 size whose walker has a diagnostics build (T2sin_size = 256)
+constexpr int WALK_PROF_LOGT = 8;
+
+bool stream_walk_has_prof(int logt) { return logt == WALK_PROF_LOGT; }
+
 template <int LOGT>
 static hipError_t walk_launch_n(const WalkArgs& a, long nblocks, hipStream_t st)
 {
     const size_t shm = walk_shm<LOGT>(a.L, a.cycles, a.tspec != nullptr);
     if (shm > 160 * 1024) return hipErrorInvalidValue;
     if ((a.iq16 != nullptr) == (a.iq != nullptr)) return hipErrorInvalidValue;  // exactly one stream format
-    if constexpr (LOGT == 8) {  // the diagnostics build of the default T2 size (OFDM_WALK_PROF)
+    if constexpr (LOGT == WALK_PROF_LOGT) {  // the diagnostics build of the default T2 size (OFDM_WALK_PROF)
         if (a.prof) {
             const void* k = a.iq16 ? (const void*)stream_walk_kernel<LOGT, true, true>
                                    : (const void*)stream_walk_kernel<LOGT, false, true>;

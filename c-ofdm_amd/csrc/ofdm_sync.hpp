@@ -275,6 +275,9 @@ hipError_t launch_stream_decode_wide(const CfoArgs& c, const StreamParamsArgs& a
                                      hipStream_t st);
 
 hipError_t launch_stream_walk(int logt, const WalkArgs& a, long nblocks, hipStream_t st);
+// whether launch_stream_walk has a diagnostics build of the walker for this
+// T2 size: only then is WalkArgs::prof written (it is ignored otherwise)
+bool stream_walk_has_prof(int logt);
 // stream walkers resident at once on the current device (occupancy of the
 // walker with this geometry's LDS: 8 per CU for the default geometries)
 long stream_walk_slots(int logt, int L, int C, bool fft);
