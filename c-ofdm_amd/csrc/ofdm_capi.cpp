@@ -1369,13 +1369,42 @@ int ofdm_t2_scan(ofdm_ctx* c, const double* iq, size_t n, long start, double* re
     return OFDM_OK;
 }
 
-// find_preamble's split scratch when the call fits it (else the
-// one-workgroup form: hv_scratch stays null).
-static void preamble_scratch(ofdm_ctx* c, size_t nstarts, ofdm::PreambleArgs& a)
+// The launch arguments of find_preamble / preamble_corr for `nstarts` start
+// indices: the context's template and lags, and its split scratch when the
+// call fits it (else the one-workgroup form: hv_scratch stays null).
+static ofdm::PreambleArgs preamble_args(ofdm_ctx* c, const double* iq, size_t n, const int* starts, size_t nstarts)
 {
-    if (nstarts > ofdm_ctx::PRE_SCRATCH_STARTS) return;
-    a.hv_scratch = c->d_pre_hv;
-    a.done = c->d_pre_done;
+    ofdm::PreambleArgs a{};
+    a.iq = reinterpret_cast<const double2*>(iq);
+    a.n = (long)n;
+    a.starts = starts;
+    a.nstarts = (long)nstarts;
+    a.templ = c->d_templ;
+    a.L = (int)c->p.pr_sin_len;
+    a.cycles = (int)(2 * c->p.t2sin_size + c->p.pr_sin_len);
+    a.level = (double)c->p.pr_level / 1000;
+    if (nstarts <= ofdm_ctx::PRE_SCRATCH_STARTS) {
+        a.hv_scratch = c->d_pre_hv;
+        a.done = c->d_pre_done;
+    }
+    return a;
+}
+
+// What launch_find_preamble would refuse, as status codes of the header,
+// before anything is issued: more start indices than one launch takes, and a
+// T2sin_size / pr_sin_len whose lags do not fit one workgroup's LDS (the
+// launcher's own arithmetic on the same arguments).
+static int preamble_fits(ofdm_ctx* c, const ofdm::PreambleArgs& a)
+{
+    if (a.nstarts > ofdm::FIND_PREAMBLE_MAX_STARTS)
+        return fail(OFDM_ERR_INVALID, "find_preamble: nstarts=%ld exceeds %ld per call", a.nstarts,
+                    ofdm::FIND_PREAMBLE_MAX_STARTS);
+    const size_t need = ofdm::find_preamble_lds(a);
+    if (need > ofdm::FIND_PREAMBLE_MAX_LDS)
+        return fail(OFDM_ERR_UNSUPPORTED, "find_preamble: T2sin_size=%ld with pr_sin_len=%ld needs %zu bytes of LDS "
+                                          "(limit %zu)", c->p.t2sin_size, c->p.pr_sin_len, need,
+                    ofdm::FIND_PREAMBLE_MAX_LDS);
+    return OFDM_OK;
 }
 
 int ofdm_find_preamble(ofdm_ctx* c, const double* iq, size_t n, const int* starts, size_t nstarts, int* idx_out,
@@ -1383,17 +1412,11 @@ int ofdm_find_preamble(ofdm_ctx* c, const double* iq, size_t n, const int* start
 {
     if (!c || !iq || (nstarts && (!starts || !idx_out))) return fail(OFDM_ERR_INVALID, "null argument");
     if (!aligned16(iq)) return fail(OFDM_ERR_INVALID, "iq must be 16-byte aligned");
-    ofdm::PreambleArgs a{};
-    a.iq = reinterpret_cast<const double2*>(iq);
-    a.n = (long)n;
-    a.starts = starts;
-    a.nstarts = (long)nstarts;
+    if (nstarts == 0) return OFDM_OK;
+    if (nstarts > (size_t)LONG_MAX) return fail(OFDM_ERR_INVALID, "find_preamble: nstarts out of range");
+    ofdm::PreambleArgs a = preamble_args(c, iq, n, starts, nstarts);
     a.idx_out = idx_out;
-    a.templ = c->d_templ;
-    a.L = (int)c->p.pr_sin_len;
-    a.cycles = (int)(2 * c->p.t2sin_size + c->p.pr_sin_len);
-    a.level = (double)c->p.pr_level / 1000;
-    preamble_scratch(c, nstarts, a);
+    if (int rc = preamble_fits(c, a)) return rc;
     hipError_t e = ofdm::launch_find_preamble(a, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "find_preamble launch");
     return OFDM_OK;
@@ -1404,23 +1427,14 @@ int ofdm_preamble_corr(ofdm_ctx* c, const double* iq, size_t n, long start, doub
     if (!c || !iq || !cor_out) return fail(OFDM_ERR_INVALID, "null argument");
     if (!aligned16(iq)) return fail(OFDM_ERR_INVALID, "iq must be 16-byte aligned");
     if (start < INT32_MIN || start > INT32_MAX) return fail(OFDM_ERR_INVALID, "start out of range");
+    int* d_start = c->d_first + 2;  // scratch word 2: the one start index
+    ofdm::PreambleArgs a = preamble_args(c, iq, n, d_start, 1);
+    a.cor_out = cor_out;
+    if (int rc = preamble_fits(c, a)) return rc;
     if (capturing((hipStream_t)stream))
         return capture_refused("ofdm_preamble_corr (it stages `start` from the host and synchronises)");
-    int* d_start = c->d_first + 2;  // scratch word 2: the one start index
     const int s32 = (int)start;
     HIP_TRY(hipMemcpyAsync(d_start, &s32, sizeof(int), hipMemcpyHostToDevice, (hipStream_t)stream));
-    ofdm::PreambleArgs a{};
-    a.iq = reinterpret_cast<const double2*>(iq);
-    a.n = (long)n;
-    a.starts = d_start;
-    a.nstarts = 1;
-    a.idx_out = nullptr;
-    a.templ = c->d_templ;
-    a.L = (int)c->p.pr_sin_len;
-    a.cycles = (int)(2 * c->p.t2sin_size + c->p.pr_sin_len);
-    a.level = (double)c->p.pr_level / 1000;
-    a.cor_out = cor_out;
-    preamble_scratch(c, 1, a);
     hipError_t e = ofdm::launch_find_preamble(a, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "preamble_corr launch");
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));  // the start word is host-staged

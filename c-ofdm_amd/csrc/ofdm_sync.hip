@@ -374,20 +374,30 @@ __global__ void __launch_bounds__(PRE_THREADS) find_preamble_kernel(PreambleArgs
     if (t == 0 && a.idx_out) a.idx_out[blockIdx.y] = *best == INT_MAX ? -10 : (int)(s + *best);
 }
 
+// split over workgroups when the caller provides the scratch, else one
+// workgroup per start index
+static int preamble_nsplit(const PreambleArgs& a) { return a.hv_scratch && a.done ? preamble_splits(a.cycles) : 1; }
+
+size_t find_preamble_lds(const PreambleArgs& a)
+{
+    const size_t C = (size_t)a.cycles, nn = C + a.L;
+    const size_t corr = sizeof(double) * C +
+                        sizeof(double2) * ((preamble_nsplit(a) > 1 ? std::min<size_t>(C, PRE_THREADS) : C) + a.L);
+    const size_t tail = sizeof(double) * (C + nn + nn + 1 + C + PRE_BATCH + PRE_THREADS / 64) + sizeof(int) * 2 +
+                        sizeof(unsigned) * ((C + 31) / 32) + 64;
+    return sizeof(double2) + std::max(corr, tail);
+}
+
 hipError_t launch_find_preamble(const PreambleArgs& a, hipStream_t st)
 {
     if (a.nstarts <= 0) return hipSuccess;
-    // split over workgroups when the caller provides the scratch, else one
-    // workgroup per start index
-    const int nsplit = a.hv_scratch && a.done ? preamble_splits(a.cycles) : 1;
-    if (a.nstarts > 65535) return hipErrorInvalidValue;
-    const size_t C = (size_t)a.cycles, nn = C + a.L;
-    const size_t corr = sizeof(double) * C + sizeof(double2) * ((nsplit > 1 ? std::min<size_t>(C, PRE_THREADS) : C) + a.L);
-    const size_t tail = sizeof(double) * (C + nn + nn + 1 + C + PRE_BATCH + PRE_THREADS / 64) + sizeof(int) * 2 +
-                        sizeof(unsigned) * ((C + 31) / 32) + 64;
-    const size_t shm = sizeof(double2) + std::max(corr, tail);
-    if (shm > 160 * 1024) return hipErrorInvalidValue;
-    lds_opt_in((const void*)find_preamble_kernel, 160 * 1024);
+    const int nsplit = preamble_nsplit(a);
+    // (the C API's entry points check both limits first and answer with their
+    // own status codes: from there these two returns are not reached)
+    if (a.nstarts > FIND_PREAMBLE_MAX_STARTS) return hipErrorInvalidValue;
+    const size_t shm = find_preamble_lds(a);
+    if (shm > FIND_PREAMBLE_MAX_LDS) return hipErrorInvalidValue;
+    lds_opt_in((const void*)find_preamble_kernel, (int)FIND_PREAMBLE_MAX_LDS);
     hipLaunchKernelGGL(find_preamble_kernel, dim3((unsigned)nsplit, (unsigned)a.nstarts), dim3(PRE_THREADS), shm, st, a);
     return hipGetLastError();
 }

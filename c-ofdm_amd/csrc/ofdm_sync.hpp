@@ -285,6 +285,13 @@ hipError_t launch_gather(const GatherArgs& a, hipStream_t st);
 hipError_t launch_t2_scan(int logn, const T2Args& a, int* first_out, hipStream_t st);
 hipError_t launch_find_preamble(const PreambleArgs& a, hipStream_t st);
 int preamble_splits(int cycles);  // workgroups per start index
+// launch_find_preamble's limits: the dynamic LDS of one workgroup for these
+// arguments (the split form where they carry the scratch) and the start
+// indices of one launch (grid.y). The entry points check both before
+// anything is issued.
+constexpr size_t FIND_PREAMBLE_MAX_LDS = 160 * 1024;
+constexpr long FIND_PREAMBLE_MAX_STARTS = 65535;
+size_t find_preamble_lds(const PreambleArgs& a);
 hipError_t launch_cfo(int logm, int g, const CfoArgs& a, hipStream_t st);
 hipError_t launch_freq_shift(const ShiftArgs& a, hipStream_t st);
 hipError_t launch_cp_sync(const CpArgs& a, hipStream_t st);

@@ -561,16 +561,26 @@ int ofdm_t2_scan(ofdm_ctx* ctx, const double* iq, size_t n, long start,
  * idx_out[i] = starts[i] + first lag whose normalised correlation with the
  * preamble template exceeds pr_level/1000 (lags 0 .. 2*T2sin_size+pr_sin_len-1,
  * running window energy updated after each test, as the reference), or -10.
- * Samples past n read as 0. Device arrays. Callers add +1 (main.cpp:53). */
+ * Samples past n read as 0, and so do the samples before 0 that a negative
+ * start reaches. Device arrays. Callers add +1 (main.cpp:53).
+ * nstarts == 0: OFDM_OK, nothing written. Before anything is issued:
+ * OFDM_ERR_INVALID for nstarts > 65535 (one launch's limit; split the batch),
+ * OFDM_ERR_UNSUPPORTED for a T2sin_size / pr_sin_len pair whose
+ * 2*T2sin_size + pr_sin_len lags do not fit one workgroup's 160 KB of LDS
+ * (every T2sin_size = 4096, which ofdm_t2_scan accepts; T2sin_size = 2048
+ * fits up to pr_sin_len = 664). idx_out is then left as it was. */
 int ofdm_find_preamble(ofdm_ctx* ctx, const double* iq, size_t n,
                        const int* starts, size_t nstarts, int* idx_out, void* stream);
 
 /* PREAMBLE_FORM::find_corr (Frame.cpp:297-335): the normalised correlation
  * at every lag from `start` (cor_out[i] = |sum x[start+i+j] c_j| / sqrt(norm_i)
  * where norm_i > 1, else 0; 2*T2sin_size + pr_sin_len lags). Device arrays.
- * Samples past n read as 0. Unlike the other compute calls this one copies
+ * Samples past n read as 0, and so do the samples before 0 that a negative
+ * start reaches. Unlike the other compute calls this one copies
  * `start` from the host and synchronises `stream` before it returns: it cannot
- * be captured (OFDM_ERR_UNSUPPORTED on a capturing stream). */
+ * be captured (OFDM_ERR_UNSUPPORTED on a capturing stream).
+ * OFDM_ERR_UNSUPPORTED, before the host copy and with cor_out left as it was,
+ * for the T2sin_size / pr_sin_len pairs ofdm_find_preamble refuses. */
 int ofdm_preamble_corr(ofdm_ctx* ctx, const double* iq, size_t n, long start, double* cor_out,
                        void* stream);
 

@@ -16,6 +16,7 @@ import pytest
 
 import oracle as O
 from common import ALL_CONFIGS, D, G, golden, payload, rel_err
+from detector_cases import find_corr_ref
 from test_gpu_sync import _impaired_frames
 
 pytestmark = pytest.mark.gpu
@@ -107,32 +108,6 @@ def test_double_to_int16(n):
 
 
 # ------------------------------------------------------------------ preamble_corr
-def find_corr_ref(x, n, start, tpl, cycles):
-    """PREAMBLE_FORM::find_corr in FP64: the running norm recurrence (the sum
-    of the first L energies, then +|x[i+L]|^2 -|x[i]|^2 after each lag, in
-    that order), the norm > 1 gate and |sum x[start+i+j] c_j| / sqrt(norm).
-    Samples outside [0, n) read as zero. Returns (cor, norms)."""
-    L = len(tpl)
-    idx = start + np.arange(cycles + L)
-    ok = (idx >= 0) & (idx < n)
-    seg = np.zeros(cycles + L, np.complex128)
-    seg[ok] = x[idx[ok]]
-    en = seg.real * seg.real + seg.imag * seg.imag
-    norm = 0.0
-    for i in range(L):
-        norm += float(en[i])
-    norms = np.empty(cycles)
-    for i in range(cycles):
-        norms[i] = norm
-        norm += float(en[i + L])
-        norm -= float(en[i])
-    corr = np.lib.stride_tricks.sliding_window_view(seg, L)[:cycles] @ tpl
-    gate = norms > 1.0
-    cor = np.zeros(cycles)
-    cor[gate] = np.abs(corr[gate]) / np.sqrt(norms[gate])
-    return cor, norms
-
-
 def test_preamble_corr():
     """ofdm_preamble_corr on the golden capture against find_corr_ref, at
     rel_err < 1e-10, entries behind a closed gate exactly 0. Starts: 0 and
