@@ -77,6 +77,13 @@ int check_stream_call(const ofdm_ctx* c, const StreamCall& a)
     if (a.own_lo < 0 || a.own_lo > a.own_hi || a.own_hi > (long)a.n)
         return fail(OFDM_ERR_INVALID, "need 0 <= own_lo <= own_hi <= n");
     if (c->t2_logn < 6 || c->t2_logn > 11) return fail(OFDM_ERR_UNSUPPORTED, "stream walk needs T2sin_size = 2^a, 64..2048");
+    // the walker's LDS, as plan_walk and launch_stream_walk will ask for it
+    const size_t lds = stream_walk_lds(c->t2_logn, (int)c->p.pr_sin_len, (int)(2 * c->p.t2sin_size + c->p.pr_sin_len),
+                                       c->d_tspec != nullptr);
+    if (lds > STREAM_WALK_MAX_LDS)
+        return fail(OFDM_ERR_UNSUPPORTED, "stream walk: T2sin_size = %ld with pr_sin_len = %ld needs %zu bytes of LDS "
+                                          "(limit %zu)", (long)c->p.t2sin_size, (long)c->p.pr_sin_len, lds,
+                    STREAM_WALK_MAX_LDS);
     if ((a.iq && !aligned16(a.iq)) || (a.iq16 && ((uintptr_t)a.iq16 & 3)) ||
         (a.constell_out && !aligned16(a.constell_out)))
         return fail(OFDM_ERR_INVALID, "misaligned buffer (complex<double> 16 B, complex<int16> 4 B)");

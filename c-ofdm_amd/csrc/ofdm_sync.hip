@@ -2823,7 +2823,7 @@ template <int LOGT>
 static hipError_t walk_launch_n(const WalkArgs& a, long nblocks, hipStream_t st)
 {
     const size_t shm = walk_shm<LOGT>(a.L, a.cycles, a.tspec != nullptr);
-    if (shm > 160 * 1024) return hipErrorInvalidValue;
+    if (shm > STREAM_WALK_MAX_LDS) return hipErrorInvalidValue;
     if ((a.iq16 != nullptr) == (a.iq != nullptr)) return hipErrorInvalidValue;  // exactly one stream format
     if constexpr (LOGT == WALK_PROF_LOGT) {  // the diagnostics build of the default T2 size (OFDM_WALK_PROF)
         if (a.prof) {
@@ -2890,6 +2890,19 @@ long stream_walk_slots(int logt, int L, int C, bool fft)
         case 10: return walk_slots_n<10>(L, C, fft);
         case 11: return walk_slots_n<11>(L, C, fft);
         default: return 256;
+    }
+}
+
+size_t stream_walk_lds(int logt, int L, int C, bool fft)
+{
+    switch (logt) {
+        case 6: return walk_shm<6>(L, C, fft);
+        case 7: return walk_shm<7>(L, C, fft);
+        case 8: return walk_shm<8>(L, C, fft);
+        case 9: return walk_shm<9>(L, C, fft);
+        case 10: return walk_shm<10>(L, C, fft);
+        case 11: return walk_shm<11>(L, C, fft);
+        default: return 0;
     }
 }
 

@@ -281,6 +281,11 @@ bool stream_walk_has_prof(int logt);
 // stream walkers resident at once on the current device (occupancy of the
 // walker with this geometry's LDS: 8 per CU for the default geometries)
 long stream_walk_slots(int logt, int L, int C, bool fft);
+// the dynamic LDS of one walker workgroup for the same arguments (0 for a T2
+// size without a walker): launch_stream_walk refuses more than
+// STREAM_WALK_MAX_LDS, and the entry points check it before anything is issued
+constexpr size_t STREAM_WALK_MAX_LDS = 160 * 1024;
+size_t stream_walk_lds(int logt, int L, int C, bool fft);
 hipError_t launch_gather(const GatherArgs& a, hipStream_t st);
 hipError_t launch_t2_scan(int logn, const T2Args& a, int* first_out, hipStream_t st);
 hipError_t launch_find_preamble(const PreambleArgs& a, hipStream_t st);

@@ -680,6 +680,14 @@ int ofdm_sync_frames(ofdm_ctx* ctx, double* frames, size_t nframes, size_t frame
  * pb_out[f] preamble start, bytes_out (bytes_per_frame per frame),
  * constell_out (D*num_symb complex per frame), cfo_out. *nframes_out = frames
  * found; outputs hold the first max_frames. The input is not modified.
+ * OFDM_ERR_UNSUPPORTED, before anything is issued (*nframes_out = 0, no output
+ * written), for a detector the walker does not take: T2sin_size = 2^a, 64..2048
+ * only, and a T2sin_size / pr_sin_len pair whose walker needs more than one
+ * workgroup's 160 KB of LDS. The direct preamble search (pr_sin_len > 449)
+ * holds 2*T2sin_size + pr_sin_len lags and about 72 bytes per template sample
+ * there, so T2sin_size = 2048 is taken up to pr_sin_len = 449 (it has no
+ * direct search), 1024 up to 1328 and 512 up to 1785. This is narrower than
+ * ofdm_find_preamble's own limit (T2sin_size = 2048 up to pr_sin_len = 664).
  * Returns once the walk is resolved (the host waits for a small status block);
  * the decode is enqueued on `stream` and may still be running, so order later
  * work on `stream`, or synchronise it, before reading the outputs. */
