@@ -158,6 +158,7 @@ __global__ void __launch_bounds__(WideGeo<LOGN>::NT, 4) stream_decode_wide_kerne
                     const long i0 = x0 + (long)q * L + j;
                     acc = cadd(acc, cconj_mul(src_sample_t<I16>(a.iq, a.iq16, i0), src_sample_t<I16>(a.iq, a.iq16, i0 + N)));
                 }
+                // wave_sum2, written out (through the call the N = 1024 int16 kernel changes)
 #pragma unroll
                 for (int o = 32; o > 0; o >>= 1) {
                     acc.x += __shfl_xor(acc.x, o);
@@ -179,28 +180,17 @@ __global__ void __launch_bounds__(WideGeo<LOGN>::NT, 4) stream_decode_wide_kerne
             tq[q] = q == 0 ? fq : cmul(fq, twk[q - 1]);
         }
         __syncthreads();  // every transform read: the spectrum overwrites them
-        // the 5-point DFT over q by the symmetric pairs (1, 4), (2, 3) (as
-        // the N = 512 kernel: W5 = (c1, n1), W5^2 = (c2, n2))
-        const double c1 = w1.x, n1 = w1.y, c2 = w2.x, n2 = w2.y;
-        const double2 a0 = tq[0];
-        const double2 s1 = make_double2(tq[1].x + tq[4].x, tq[1].y + tq[4].y);
-        const double2 d1 = make_double2(tq[1].x - tq[4].x, tq[1].y - tq[4].y);
-        const double2 s2 = make_double2(tq[2].x + tq[3].x, tq[2].y + tq[3].y);
-        const double2 d2 = make_double2(tq[2].x - tq[3].x, tq[2].y - tq[3].y);
-        const double2 t1 = make_double2(a0.x + c1 * s1.x + c2 * s2.x, a0.y + c1 * s1.y + c2 * s2.y);
-        const double2 t2 = make_double2(a0.x + c2 * s1.x + c1 * s2.x, a0.y + c2 * s1.y + c1 * s2.y);
-        const double2 u1 = make_double2(n1 * d1.x + n2 * d2.x, n1 * d1.y + n2 * d2.y);
-        const double2 u2 = make_double2(n2 * d1.x - n1 * d2.x, n2 * d1.y - n1 * d2.y);
-        const double2 X[G] = {make_double2(a0.x + s1.x + s2.x, a0.y + s1.y + s2.y),
-                              make_double2(t1.x - u1.y, t1.y + u1.x), make_double2(t2.x - u2.y, t2.y + u2.x),
-                              make_double2(t2.x + u2.y, t2.y - u2.x), make_double2(t1.x + u1.y, t1.y - u1.x)};
+        double2 X[G];
+        radix5_combine(tq, w1, w2, X);  // W5 = w1, W5^2 = w2
         double2* spec = A;
 #pragma unroll
         for (int q = 0; q < G; ++q) spec[(tid + M * q + S5 / 2) % S5] = X[q];
         __syncthreads();  // spectrum visible
         // first argmax of |X| = hypot in each pilot window [borders[i],
         // borders[i+1]), i != P/2 (std::max_element), decided on |X|^2 where
-        // the runner-up is certainly below (the N = 512 kernel's rule)
+        // the runner-up is certainly below: window_argmax_screened<NT> and
+        // cfo_from_windows (ofdm_syncdev.hpp), written out here because this
+        // kernel's instruction count changes through the calls
         constexpr int AG = 8;
         constexpr double SURE = 1.0 - 64.0 * 0x1.0p-53;
         for (int g0 = 0; g0 < c.P; g0 += NT / AG) {
@@ -291,7 +281,6 @@ __global__ void __launch_bounds__(WideGeo<LOGN>::NT, 4) stream_decode_wide_kerne
 
     // ------------------------------------------------------------ preamble (group 0)
     const bool g0 = tid < T;  // wave-uniform
-    double b, aa;
     {
         const int t = tid;
         double2 z[LT], pz = make_double2(0.0, 0.0), dz[4], mpre[4], prc[CT];
@@ -363,17 +352,7 @@ __global__ void __launch_bounds__(WideGeo<LOGN>::NT, 4) stream_decode_wide_kerne
         }
         acc = block_sum2<NT>(acc, red);  // group 1 adds zeros
         const double phr = atan2_fast(acc.y, acc.x);
-        // e^{-i phr} = conj(acc) / |acc| (uniform; sincos for a zero or non-finite sum)
-        double2 rot;
-        const double ha = hypot(acc.x, acc.y);
-        if (ha > 0.0 && ha <= DBL_MAX) {
-            const double ir = 1.0 / ha;
-            rot = make_double2(acc.x * ir, -acc.y * ir);
-        } else {
-            double rs2, rc2;
-            sincos(-phr, &rs2, &rc2);
-            rot = make_double2(rc2, rs2);
-        }
+        const double2 rot = unit_conj(acc, phr);  // e^{-i phr}
         if (t == 0) misc[1] = rot;
         if (g0) {
             if (t < P) spil[t] = cmul_exact(pz, rot);
@@ -390,7 +369,7 @@ __global__ void __launch_bounds__(WideGeo<LOGN>::NT, 4) stream_decode_wide_kerne
         const double phys = acc / ((double)P * a.pilot_ampl);
         // arg((F/phys)/coef/mod_pre) (Frame.hpp:397-405): for a finite
         // positive phys arg(F conj(mod_pre)) (coef is 1 to the last bit);
-        // otherwise the reference's divisions verbatim
+        // otherwise the reference's divisions verbatim (sync_frame's lines)
         const bool plain = phys > 0.0 && phys <= DBL_MAX;  // uniform
         if (tid < half) {  // half <= NT (D <= 4T)
             const double2 mp = a.mod_pre[tid];
@@ -399,29 +378,15 @@ __global__ void __launch_bounds__(WideGeo<LOGN>::NT, 4) stream_decode_wide_kerne
                 q = cmul_exact(dat[tid], make_double2(mp.x, -mp.y));
             } else {
                 const int j = a.tab.data_slot[tid];
-                const double2 p0 = make_double2(spil[j].x / phys, spil[j].y / phys);
-                const double2 coef = cdiv_exact(p0, p0);
-                const double2 fs = make_double2(dat[tid].x / phys, dat[tid].y / phys);
-                q = cdiv_exact(cdiv_exact(fs, coef), mp);
+                q = preamble_ratio(spil[j], dat[tid], mp, phys);
             }
             ph[tid] = atan2_fast(q.y, q.x);
         }
     }
     __syncthreads();
     unwrap_scan<NT>(ph, half, reinterpret_cast<unsigned*>(red + 16));  // one-pass unwrap (Frame.hpp:407-414)
-    {
-        double sxy = 0.0, sy = 0.0;
-        for (int i = tid; i < half; i += NT) {
-            sxy += ph[i] * i;
-            sy += ph[i];
-        }
-        const double2 sums = block_sum2<NT>(make_double2(sxy, sy), red);
-        const double hn = (double)half;
-        const double sx = hn * (hn - 1) / 2, sx2 = (hn - 1) * hn * (2 * hn - 1) / 6;
-        b = (sums.x - sx * sums.y) / (sx2 - sx * sx);
-        aa = sums.y - b * sx;
-    }
-    if (tid == 0) misc[0] = make_double2(b, aa);
+    const double2 fit = phase_line_fit<NT>(ph, half, tid, red);
+    if (tid == 0) misc[0] = fit;
     __syncthreads();  // the table visible; the sync arrays are free
     __builtin_amdgcn_s_setprio(0);
 
@@ -504,13 +469,8 @@ __global__ void __launch_bounds__(WideGeo<LOGN>::NT, 4) stream_decode_wide_kerne
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
         const int d = tid + NT * u;
-        double th;
-        if (d < half)
-            th = add_rn(mul_rn(ba.x, (double)d), ba.y);
-        else
-            th = add_rn(add_rn(mul_rn(-ba.x, (double)D) / 2, mul_rn((double)(d - half), ba.x)), ba.y);
         double sn, cs;
-        sincos(th, &sn, &cs);
+        sincos(chan_line_angle(ba.x, ba.y, half, D, d), &sn, &cs);
         chv[u] = cmul_exact(make_double2(cs, -sn), rot);  // and pr_phase_sinh's e^{-i phi_pr}
     }
     // phys_pilot_ampl = sum |pilot| / (P*S*pilot_ampl)   (Frame.cpp:76-80)

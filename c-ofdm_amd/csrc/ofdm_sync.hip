@@ -25,6 +25,7 @@
 #include <cfloat>
 #include <climits>
 #include <cstdint>
+#include <type_traits>
 
 #include "ofdm_dev.hpp"
 #include "ofdm_fft.hpp"
@@ -40,6 +41,17 @@
 namespace ofdm {
 
 constexpr int SYNC_THREADS = 256;
+
+// f(std::integral_constant<int, logn>) for LO <= logn <= HI: the launchers'
+// choice of the kernel instance; hipErrorInvalidValue outside the range.
+template <int LO, int HI, class F>
+static hipError_t dispatch_logn(int logn, const F& f)
+{
+    if constexpr (LO > HI)
+        return hipErrorInvalidValue;
+    else
+        return logn == LO ? f(std::integral_constant<int, LO>{}) : dispatch_logn<LO + 1, HI>(logn, f);
+}
 
 // ========================================================================
 // T2 detector: G transforms of N = 2^LOGN points per workgroup.
@@ -151,18 +163,7 @@ hipError_t launch_t2_scan(int logn, const T2Args& a0, int* first_out, hipStream_
     T2Args a = a0;
     a.first_out = first_out;
     hipError_t e = hipSuccess;
-    if (a.nblocks > 0) {
-        switch (logn) {
-            case 6: e = t2_launch_n<6>(a, st); break;
-            case 7: e = t2_launch_n<7>(a, st); break;
-            case 8: e = t2_launch_n<8>(a, st); break;
-            case 9: e = t2_launch_n<9>(a, st); break;
-            case 10: e = t2_launch_n<10>(a, st); break;
-            case 11: e = t2_launch_n<11>(a, st); break;
-            case 12: e = t2_launch_n<12>(a, st); break;
-            default: return hipErrorInvalidValue;
-        }
-    }
+    if (a.nblocks > 0) e = dispatch_logn<6, 12>(logn, [&](auto k) { return t2_launch_n<decltype(k)::value>(a, st); });
     if (e != hipSuccess) return e;
     if (first_out && a.nblocks <= 0) {  // no block to scan: -1 (the scratch holds INT_MAX)
         hipLaunchKernelGGL(t2_finalize_kernel, dim3(1), dim3(1), 0, st, a.first_scratch, first_out, a.start,
@@ -486,11 +487,8 @@ __global__ void __launch_bounds__(G * (1 << LOGM) / 8) cfo_kernel(CfoArgs a)
     }
     __syncthreads();
     // first argmax inside each pilot window [borders[i], borders[i+1]), i != P/2
-    // (std::max_element: strictly-greater keeps the first maximum). A group
-    // of AG lanes per window: each lane the first maximum of its strided
-    // share, then a butterfly keeping the larger value, the lower index on
-    // ties, which is the window's first maximum.
-    constexpr int AG = 8;
+    // (std::max_element), a group of AG lanes per window
+    constexpr int AG = ARGMAX_LANES;
     for (int i0 = 0; i0 <= a.P; i0 += NT / AG) {
         const int i = i0 + tid / AG, l = tid % AG;
         const bool act = tid < (NT / AG) * AG && i <= a.P;
@@ -499,35 +497,14 @@ __global__ void __launch_bounds__(G * (1 << LOGM) / 8) cfo_kernel(CfoArgs a)
             lo = a.borders[i];
             hi = a.borders[i + 1];
         }
-        double bv = -1.0;  // below every magnitude
-        int bi = INT_MAX;
-        for (int j = lo + l; j < hi; j += AG)
-            if (bv < amp[j]) {
-                bv = amp[j];
-                bi = j;
-            }
-#pragma unroll
-        for (int o = 1; o < AG; o <<= 1) {  // AG-lane groups are aligned within a wave
-            const double ov = __shfl_xor(bv, o);
-            const int oi = __shfl_xor(bi, o);
-            if (ov > bv || (ov == bv && oi < bi)) {
-                bv = ov;
-                bi = oi;
-            }
-        }
+        const int bi = window_first_max(lo, hi, l, [&](int j) { return amp[j]; });
         // max_element of an empty range = end; a NaN first element is kept
         // (nothing compares greater than it)
         if (act && l == 0) wsum[i] = lo < hi ? (isnan(amp[lo]) ? lo : bi) : hi;
     }
     __syncthreads();
     if (tid == 0) {
-        double shift = 0.0;
-        for (int i = 0; i <= a.P; ++i)
-            if (i != a.P / 2) shift += wsum[i];
-        shift /= a.P;
-        shift -= S / 2;
-        shift /= S;
-        a.cfo_out[f] = shift;
+        a.cfo_out[f] = cfo_from_windows(wsum, a.P, S);
         if (a.host_out) __threadfence_system();  // a pinned host word its caller polls
     }
 }
@@ -548,28 +525,8 @@ static hipError_t cfo_launch_n(const CfoArgs& a, hipStream_t st)
 hipError_t launch_cfo(int logm, int g, const CfoArgs& a, hipStream_t st)
 {
     if (a.nframes <= 0) return hipSuccess;
-    if (g == 1) {
-        switch (logm) {
-            case 6: return cfo_launch_n<6, 1>(a, st);
-            case 7: return cfo_launch_n<7, 1>(a, st);
-            case 8: return cfo_launch_n<8, 1>(a, st);
-            case 9: return cfo_launch_n<9, 1>(a, st);
-            case 10: return cfo_launch_n<10, 1>(a, st);
-            case 11: return cfo_launch_n<11, 1>(a, st);
-            case 12: return cfo_launch_n<12, 1>(a, st);
-            default: return hipErrorInvalidValue;
-        }
-    }
-    if (g == 5) {
-        switch (logm) {
-            case 6: return cfo_launch_n<6, 5>(a, st);
-            case 7: return cfo_launch_n<7, 5>(a, st);
-            case 8: return cfo_launch_n<8, 5>(a, st);
-            case 9: return cfo_launch_n<9, 5>(a, st);
-            case 10: return cfo_launch_n<10, 5>(a, st);
-            default: return hipErrorInvalidValue;
-        }
-    }
+    if (g == 1) return dispatch_logn<6, 12>(logm, [&](auto k) { return cfo_launch_n<decltype(k)::value, 1>(a, st); });
+    if (g == 5) return dispatch_logn<6, 10>(logm, [&](auto k) { return cfo_launch_n<decltype(k)::value, 5>(a, st); });
     return hipErrorInvalidValue;
 }
 
@@ -630,24 +587,15 @@ __global__ void __launch_bounds__(CP_THREADS) cp_sync_kernel(CpArgs a)
     const long f = blockIdx.x;
     double2* x = a.x + f * a.frame_stride;
     const int t = threadIdx.x, lane = t & 63, w = t >> 6, L = a.N + a.cp;
+    // (sync_chain_kernel runs this stage on its LDS copy with 32-bit indices)
     for (int s = w; s < a.nsym; s += CP_THREADS / 64) {
         double2 acc = make_double2(0.0, 0.0);
         for (int j = lane; j < a.cp; j += 64) acc = cadd(acc, cconj_mul(x[(long)s * L + j], x[(long)s * L + j + a.N]));
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            acc.x += __shfl_xor(acc.x, o);
-            acc.y += __shfl_xor(acc.y, o);
-        }
+        acc = wave_sum2(acc);
         if (lane == 0) phi[s] = atan2(acc.y, acc.x);
     }
     __syncthreads();
-    if (t == 0) {  // psi_s = phi_0 + ... + phi_{s-1}, in that order (Frame.hpp:257-260)
-        double p = 0.0;
-        for (int q = 0; q < a.nsym; ++q) {
-            psi[q] = p;
-            p += phi[q];
-        }
-    }
+    if (t == 0) phase_prefix(phi, psi, a.nsym);
     __syncthreads();
     const long total = (long)a.nsym * L;
     for (long n = t; n < total; n += CP_THREADS) {
@@ -729,24 +677,15 @@ __global__ void __launch_bounds__(CHAIN_THREADS) sync_chain_kernel(SyncChainArgs
         if (a.out[0]) a.out[0][off + n] = v;
     }
     __syncthreads();
+    // cp_sync_kernel's stage (there with 64-bit indices into global memory)
     for (int s = w; s < a.nsym; s += CHAIN_THREADS / 64) {
         double2 acc = make_double2(0.0, 0.0);
         for (int j = lane; j < a.cp; j += 64) acc = cadd(acc, cconj_mul(xs[s * L + j], xs[s * L + j + a.N]));
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            acc.x += __shfl_xor(acc.x, o);
-            acc.y += __shfl_xor(acc.y, o);
-        }
+        acc = wave_sum2(acc);
         if (lane == 0) phi[s] = atan2(acc.y, acc.x);
     }
     __syncthreads();
-    if (t == 0) {
-        double p = 0.0;
-        for (int q = 0; q < a.nsym; ++q) {
-            psi[q] = p;
-            p += phi[q];
-        }
-    }
+    if (t == 0) phase_prefix(phi, psi, a.nsym);
     __syncthreads();
     const long total = (long)a.nsym * L;
     for (long n = t; n < ns; n += CHAIN_THREADS) {
@@ -764,11 +703,7 @@ __global__ void __launch_bounds__(CHAIN_THREADS) sync_chain_kernel(SyncChainArgs
     if (t < SYNC_THREADS) {
         double2 acc = make_double2(0.0, 0.0);
         for (long i = t; i < a.pr_len; i += SYNC_THREADS) acc = cadd(acc, cconj_mul(a.pr[i], xs[i]));
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            acc.x += __shfl_xor(acc.x, o);
-            acc.y += __shfl_xor(acc.y, o);
-        }
+        acc = wave_sum2(acc);
         if (lane == 0) red[w] = acc;
     }
     __syncthreads();
@@ -848,6 +783,7 @@ __global__ void __launch_bounds__((1 << LOGN) / 8) chan_kernel(ChanArgs a)
     const double phys = acc / ((double)(a.P * a.npr) * a.pilot_ampl);
     // pr[i] = (F/phys) / coef, coef = (F[0,p]/phys)/(F[0,p]/phys); phase of pr/mod
     for (int i = t; i < half; i += T) {
+        // (preamble_ratio, written out: through the call this kernel takes more VGPRs)
         const int j = a.tab.data_slot[i];
         const double2 p0 = make_double2(pil[j].x / phys, pil[j].y / phys);
         const double2 coef = cdiv_exact(p0, p0);
@@ -857,26 +793,11 @@ __global__ void __launch_bounds__((1 << LOGN) / 8) chan_kernel(ChanArgs a)
     }
     __syncthreads();
     unwrap_scan<T>(ph, half, reinterpret_cast<unsigned*>(red) + 96);  // one-pass unwrap (Frame.hpp:407-414)
-    double sxy = 0.0, sy = 0.0;
-    for (int i = t; i < half; i += T) {
-        sxy += ph[i] * i;
-        sy += ph[i];
-    }
-    const double2 sums = block_sum2<T>(make_double2(sxy, sy), reinterpret_cast<double2*>(red) + 16);
-    // integer sums are exact in any order
-    const double hn = (double)half;
-    const double sx = hn * (hn - 1) / 2, sx2 = (hn - 1) * hn * (2 * hn - 1) / 6;
-    const double b = (sums.x - sx * sums.y) / (sx2 - sx * sx);
-    const double aa = sums.y - b * sx;
+    const double2 ba = phase_line_fit<T>(ph, half, t, reinterpret_cast<double2*>(red) + 16);
     double2* chan = a.chan_out + f * a.chan_stride;
     for (int i = t; i < a.D; i += T) {
-        double th;
-        if (i < half)
-            th = add_rn(mul_rn(b, (double)i), aa);
-        else
-            th = add_rn(add_rn(mul_rn(-b, (double)a.D) / 2, mul_rn((double)(i - half), b)), aa);
         double sn, cs;
-        sincos(th, &sn, &cs);
+        sincos(chan_line_angle(ba.x, ba.y, half, a.D, i), &sn, &cs);
         chan[i] = make_double2(cs, sn);
     }
 }
@@ -896,16 +817,7 @@ static hipError_t chan_launch_n(const ChanArgs& a, hipStream_t st)
 hipError_t launch_chan(int logn, const ChanArgs& a, hipStream_t st)
 {
     if (a.nframes <= 0) return hipSuccess;
-    switch (logn) {
-        case 6: return chan_launch_n<6>(a, st);
-        case 7: return chan_launch_n<7>(a, st);
-        case 8: return chan_launch_n<8>(a, st);
-        case 9: return chan_launch_n<9>(a, st);
-        case 10: return chan_launch_n<10>(a, st);
-        case 11: return chan_launch_n<11>(a, st);
-        case 12: return chan_launch_n<12>(a, st);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_logn<6, 12>(logn, [&](auto k) { return chan_launch_n<decltype(k)::value>(a, st); });
 }
 
 // ========================================================================
@@ -986,12 +898,7 @@ __global__ void __launch_bounds__((1 << LOGN) / 8, 3) stream_params_kernel(Strea
     double2* part = dat;  // Q*NWV wave partials (dat is filled only later)
     const int lane = t & 63, wv = t >> 6;
     auto wave_part = [&](int q, double2 acc) {
-        constexpr int W0 = T >= 64 ? 32 : T / 2;
-#pragma unroll
-        for (int o = W0; o > 0; o >>= 1) {
-            acc.x += __shfl_xor(acc.x, o);
-            acc.y += __shfl_xor(acc.y, o);
-        }
+        acc = wave_sum2<(T >= 64 ? 32 : T / 2)>(acc);
         if (lane == 0) part[q * NWV + wv] = acc;
     };
     double rs, rc;
@@ -1004,7 +911,8 @@ __global__ void __launch_bounds__((1 << LOGN) / 8, 3) stream_params_kernel(Strea
         wave_part(0, acc);
     }
     // two symbols per iteration, so both symbols' CP loads are in flight
-    // together (the shuffles in wave_part keep the compiler from unrolling)
+    // together (the shuffles in wave_part keep the compiler from unrolling).
+    // sync_frame's wave 1 runs the same loop.
     for (int q = 1; q < Q; q += 2) {
         const bool two = q + 1 < Q;  // uniform
         double2 acc0 = make_double2(0.0, 0.0), acc1 = make_double2(0.0, 0.0);
@@ -1026,13 +934,7 @@ __global__ void __launch_bounds__((1 << LOGN) / 8, 3) stream_params_kernel(Strea
         phi[q] = cp_phase(acc, make_double2(rc, rs));
     }
     __syncthreads();
-    if (t == 0) {
-        double acc = 0.0;
-        for (int q = 0; q < Q; ++q) {
-            psi[q] = acc;
-            acc += phi[q];
-        }
-    }
+    if (t == 0) phase_prefix(phi, psi, Q);
     // freq_shift + cp_freq_sinh on the preamble: theta(j) = slope * j (psi_0 = 0),
     // applied as e^{i slope t} * (e^{i slope T})^r. pr_phase_sinh's sum
     // sum_{i<L} conj(pre_i) z_i is taken as its CP share in time plus its body
@@ -1100,35 +1002,17 @@ __global__ void __launch_bounds__((1 << LOGN) / 8, 3) stream_params_kernel(Strea
     for (int u = 0; u < 2; ++u) {
         const int i = t + T * u;
         if (i < half) {
-            const int j = dslot[u];
-            const double2 p0 = make_double2(pil[j].x / phys, pil[j].y / phys);
-            const double2 coef = cdiv_exact(p0, p0);
-            const double2 fs = make_double2(dat[i].x / phys, dat[i].y / phys);
-            const double2 q = cdiv_exact(cdiv_exact(fs, coef), mpre[u]);
+            const double2 q = preamble_ratio(pil[dslot[u]], dat[i], mpre[u], phys);
             ph[i] = atan2_fast(q.y, q.x);
         }
     }
     __syncthreads();
     unwrap_scan<T>(ph, half, reinterpret_cast<unsigned*>(red + 24));  // one-pass unwrap (Frame.hpp:407-414)
-    double sxy = 0.0, sy = 0.0;
-    for (int i = t; i < half; i += T) {
-        sxy += ph[i] * i;
-        sy += ph[i];
-    }
-    const double2 sums = block_sum2<T>(make_double2(sxy, sy), red + 16);
-    const double hn = (double)half;
-    const double sx = hn * (hn - 1) / 2, sx2 = (hn - 1) * hn * (2 * hn - 1) / 6;
-    const double b = (sums.x - sx * sums.y) / (sx2 - sx * sx);
-    const double aa = sums.y - b * sx;
+    const double2 ba = phase_line_fit<T>(ph, half, t, red + 16);
     double2* chan = a.chan_out + f * a.D;
     for (int i = t; i < a.D; i += T) {
-        double th;
-        if (i < half)
-            th = add_rn(mul_rn(b, (double)i), aa);
-        else
-            th = add_rn(add_rn(mul_rn(-b, (double)a.D) / 2, mul_rn((double)(i - half), b)), aa);
         double sn, cs;
-        sincos(th, &sn, &cs);
+        sincos(chan_line_angle(ba.x, ba.y, half, a.D, i), &sn, &cs);
         // the reciprocal once per carrier (libgcc division, as the caller's
         // constell /= chan would round it) instead of a division per point
         chan[i] = a.chan_recip ? cdiv_exact(make_double2(1.0, 0.0), make_double2(cs, sn)) : make_double2(cs, sn);
@@ -1167,16 +1051,7 @@ hipError_t launch_stream_params(int logn, const StreamParamsArgs& a, hipStream_t
     const int T = (1 << logn) / 8, L = (1 << logn) + a.cp;
     if (a.npr != 1 || a.S + 1 > 64 || L % T != 0 || L / T > 16 || a.cp > 2 * T || a.D > 4 * T || a.P > T)
         return hipErrorInvalidValue;
-    switch (logn) {
-        case 6: return params_launch_n<6>(a, st);
-        case 7: return params_launch_n<7>(a, st);
-        case 8: return params_launch_n<8>(a, st);
-        case 9: return params_launch_n<9>(a, st);
-        case 10: return params_launch_n<10>(a, st);
-        case 11: return params_launch_n<11>(a, st);
-        case 12: return params_launch_n<12>(a, st);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_logn<6, 12>(logn, [&](auto k) { return params_launch_n<decltype(k)::value>(a, st); });
 }
 
 // ========================================================================
@@ -1285,111 +1160,20 @@ __device__ __forceinline__ void sync_frame(const CfoArgs& c, const StreamParamsA
                 tq[q] = q == 0 ? fq : cmul(fq, twk[q - 1]);
             }
             __syncthreads();  // every transform read: the spectrum overwrites them
-            // the 5-point DFT over q by the symmetric pairs (1, 4), (2, 3):
-            // X_r, X_{5-r} = t_r +- i u_r, with W5 = twg[0] = (c1, n1), W5^2 =
-            // twg[1] = (c2, n2) (44 operations instead of 20 products + sums)
-            static_assert(G == 5, "radix-5 combine");
-            const double c1 = twg[0].x, n1 = twg[0].y, c2 = twg[1].x, n2 = twg[1].y;
-            const double2 a0 = tq[0];
-            const double2 s1 = make_double2(tq[1].x + tq[4].x, tq[1].y + tq[4].y);
-            const double2 d1 = make_double2(tq[1].x - tq[4].x, tq[1].y - tq[4].y);
-            const double2 s2 = make_double2(tq[2].x + tq[3].x, tq[2].y + tq[3].y);
-            const double2 d2 = make_double2(tq[2].x - tq[3].x, tq[2].y - tq[3].y);
-            const double2 t1 = make_double2(a0.x + c1 * s1.x + c2 * s2.x, a0.y + c1 * s1.y + c2 * s2.y);
-            const double2 t2 = make_double2(a0.x + c2 * s1.x + c1 * s2.x, a0.y + c2 * s1.y + c1 * s2.y);
-            const double2 u1 = make_double2(n1 * d1.x + n2 * d2.x, n1 * d1.y + n2 * d2.y);
-            const double2 u2 = make_double2(n2 * d1.x - n1 * d2.x, n2 * d1.y - n1 * d2.y);
-            const double2 X[G] = {make_double2(a0.x + s1.x + s2.x, a0.y + s1.y + s2.y),
-                                  make_double2(t1.x - u1.y, t1.y + u1.x), make_double2(t2.x - u2.y, t2.y + u2.x),
-                                  make_double2(t2.x + u2.y, t2.y - u2.x), make_double2(t1.x + u1.y, t1.y - u1.x)};
+            double2 X[G];
+            radix5_combine(tq, twg[0], twg[1], X);  // W5 = twg[0], W5^2 = twg[1]
 #pragma unroll
             for (int r = 0; r < G; ++r) spec[(k + M * r + half5) % S5] = X[r];
         }
         __syncthreads();  // spectrum visible
-        // first argmax of |X| = hypot inside each pilot window [borders[i],
-        // borders[i+1]), i != P/2 (std::max_element: 8-lane groups, the larger
-        // value, the lower index on ties). Decided on e = |X|^2 (two products,
-        // one sum: relative error <= 2u, u = 2^-53) where the runner-up e2 <
-        // e1 * (1 - 64u): then every other element's hypot (error <= 4u) is
-        // strictly below the winner's, so the winner is hypot's first maximum.
-        // Otherwise (near-ties, or a non-finite element) the group takes
-        // hypot of its window, as cfo_kernel does.
+        // first argmax of |X| = hypot inside each pilot window, decided on
+        // |X|^2 where that is certain
         OFDM_PHASE(cfo_argmax);
-        constexpr int AG = 8;
-        constexpr double SURE = 1.0 - 64.0 * 0x1.0p-53;
-        // the P windows that count (window P/2 is skipped by the sum below),
-        // 8 lanes each: for P <= 8 wave 0 alone, and a wave whose groups are
-        // all past the last window skips the pass (a uniform branch)
-        for (int g0 = 0; g0 < c.P; g0 += 128 / AG) {
-            if (g0 + w * (64 / AG) >= c.P) continue;  // uniform per wave
-            const int gi = g0 + tid / AG, l = tid % AG;
-            const int i = gi < c.P / 2 ? gi : gi + 1;
-            const bool act = gi < c.P;
-            int lo = 0, hi = 0;
-            if (act) {
-                lo = c.borders[i];
-                hi = c.borders[i + 1];
-            }
-            double bv = -1.0, sv = -1.0;  // best and runner-up |X|^2 (below every magnitude)
-            int bi = INT_MAX, odd = 0;
-            for (int j = lo + l; j < hi; j += AG) {
-                const double2 z = spec[j];
-                const double e = add_rn(mul_rn(z.x, z.x), mul_rn(z.y, z.y));
-                odd |= !(e <= DBL_MAX);  // NaN or inf: hypot decides
-                if (bv < e) {
-                    sv = bv;
-                    bv = e;
-                    bi = j;
-                } else if (sv < e) {
-                    sv = e;
-                }
-            }
-#pragma unroll
-            for (int o = 1; o < AG; o <<= 1) {
-                const double ov = __shfl_xor(bv, o), os = __shfl_xor(sv, o);
-                const int oi = __shfl_xor(bi, o);
-                odd |= __shfl_xor(odd, o);
-                if (ov > bv || (ov == bv && oi < bi)) {
-                    sv = fmax(bv, fmax(sv, os));
-                    bv = ov;
-                    bi = oi;
-                } else {
-                    sv = fmax(sv, fmax(ov, os));
-                }
-            }
-            bool first_nan = false;
-            if (odd || !(sv < bv * SURE)) {  // uniform within the 8-lane group
-                bv = -1.0;
-                bi = INT_MAX;
-                for (int j = lo + l; j < hi; j += AG) {
-                    const double h = hypot(spec[j].x, spec[j].y);
-                    if (bv < h) {
-                        bv = h;
-                        bi = j;
-                    }
-                }
-#pragma unroll
-                for (int o = 1; o < AG; o <<= 1) {
-                    const double ov = __shfl_xor(bv, o);
-                    const int oi = __shfl_xor(bi, o);
-                    if (ov > bv || (ov == bv && oi < bi)) {
-                        bv = ov;
-                        bi = oi;
-                    }
-                }
-                first_nan = lo < hi && isnan(hypot(spec[lo].x, spec[lo].y));
-            }
-            if (act && l == 0) wsum[i] = lo < hi ? (first_nan ? lo : bi) : hi;
-        }
+        window_argmax_screened<128>(spec, c.borders, c.P, wsum, tid, w);
         __syncthreads();  // window maxima visible
         OFDM_PHASE(cfo_final);
         if (tid == 0) {
-            double shift = 0.0;
-            for (int i = 0; i <= c.P; ++i)
-                if (i != c.P / 2) shift += wsum[i];
-            shift /= c.P;
-            shift -= S5 / 2;
-            shift /= S5;
+            const double shift = cfo_from_windows(wsum, c.P, S5);
             scal[0] = shift;
             c.cfo_out[f] = shift;
         }
@@ -1428,12 +1212,7 @@ __device__ __forceinline__ void sync_frame(const CfoArgs& c, const StreamParamsA
 #pragma unroll
             for (int r = 0; r < RMAX; ++r)
                 if (r < CT && r + N / T < RMAX) acc = cadd(acc, cconj_mul(z[r], z[r + N / T]));
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                acc.x += __shfl_xor(acc.x, o);
-                acc.y += __shfl_xor(acc.y, o);
-            }
-            acc = cadd(make_double2(0.0, 0.0), acc);
+            acc = cadd(make_double2(0.0, 0.0), wave_sum2(acc));
             if (t == 0) phi[0] = cp_phase(acc, make_double2(rc, rs));
         }
         wave_lds_sync();
@@ -1486,18 +1265,7 @@ __device__ __forceinline__ void sync_frame(const CfoArgs& c, const StreamParamsA
             acc = cadd(acc, make_double2(bacc.x * isn, bacc.y * isn));
             acc = block_sum2<T>(acc, red);
             phr = atan2_fast(acc.y, acc.x);
-            // e^{-i phr} = conj(acc) / |acc| (acc is uniform: a uniform
-            // branch keeps sincos for a zero or non-finite sum)
-            double2 rot;
-            const double ha = hypot(acc.x, acc.y);
-            if (ha > 0.0 && ha <= DBL_MAX) {
-                const double ir = 1.0 / ha;
-                rot = make_double2(acc.x * ir, -acc.y * ir);
-            } else {
-                double rs2, rc2;
-                sincos(-phr, &rs2, &rc2);
-                rot = make_double2(rc2, rs2);
-            }
+            const double2 rot = unit_conj(acc, phr);  // e^{-i phr}
             if (t < a.P) pil[t] = cmul_exact(pz, rot);
 #pragma unroll
             for (int u = 0; u < 2; ++u)
@@ -1513,7 +1281,7 @@ __device__ __forceinline__ void sync_frame(const CfoArgs& c, const StreamParamsA
         // Frame.cpp:82-93): only the angle is used, so for a finite positive
         // phys it is arg(F conj(mod_pre)) (a positive real factor apart; coef
         // is 1 to the last bit, below); otherwise the reference's divisions
-        // verbatim
+        // verbatim. (stream_decode_wide_kernel has the same lines.)
         const bool plain = phys > 0.0 && phys <= DBL_MAX;  // uniform
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
@@ -1526,7 +1294,7 @@ __device__ __forceinline__ void sync_frame(const CfoArgs& c, const StreamParamsA
                     // up to its last bit (Smith's division of a number by
                     // itself): its angle, ~1e-16, is dropped with the division
                     q = cmul_exact(dat[i], make_double2(mpre[u].x, -mpre[u].y));
-                } else {
+                } else {  // preamble_ratio, written out (this kernel's code is pinned)
                     const double2 p0 = make_double2(pil[j].x / phys, pil[j].y / phys);
                     const double2 coef = cdiv_exact(p0, p0);
                     const double2 fs = make_double2(dat[i].x / phys, dat[i].y / phys);
@@ -1538,6 +1306,8 @@ __device__ __forceinline__ void sync_frame(const CfoArgs& c, const StreamParamsA
         wave_lds_sync();
         OFDM_PHASE(w0_pre_unwrap_ls);
         unwrap_scan<T, true>(ph, half, reinterpret_cast<unsigned*>(red + 24));  // one-pass unwrap (Frame.hpp:407-414)
+        // phase_line_fit<T>, written out (through the call this kernel comes
+        // out an instruction shorter, and its code is pinned)
         double sxy = 0.0, sy = 0.0;
         for (int i = t; i < half; i += T) {
             sxy += ph[i] * i;
@@ -1554,7 +1324,9 @@ __device__ __forceinline__ void sync_frame(const CfoArgs& c, const StreamParamsA
         }
     } else {
         // ---------------------------------------------------------- message CP sums (wave 1)
-        // two symbols per iteration, so both symbols' CP loads are in flight together
+        // two symbols per iteration, so both symbols' CP loads are in flight
+        // together (stream_params_kernel's loop; as one function the two
+        // kernels' code changes, whichever of their two store orders it takes)
         OFDM_PHASE(w1_msg_cpsums);
         const int t = lane;
         for (int q = 1; q < Q; q += 2) {
@@ -1569,7 +1341,7 @@ __device__ __forceinline__ void sync_frame(const CfoArgs& c, const StreamParamsA
                 acc1 = cadd(acc1, cconj_mul(a1, b1));
             }
 #pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
+            for (int o = 32; o > 0; o >>= 1) {  // wave_sum2 of both, interleaved
                 acc0.x += __shfl_xor(acc0.x, o);
                 acc0.y += __shfl_xor(acc0.y, o);
                 acc1.x += __shfl_xor(acc1.x, o);
@@ -1594,7 +1366,7 @@ __device__ __forceinline__ void sync_frame(const CfoArgs& c, const StreamParamsA
     __syncthreads();  // cfo, phi[0..S], phr and the LS fit visible
     OFDM_PHASE(ramp_table);
     const double cfo = scal[0], phr = scal[1], b = scal[2], aa = scal[3];
-    if (tid == 0) {
+    if (tid == 0) {  // phase_prefix, written out (through the call this kernel's SGPR count changes)
         double acc = 0.0;
         for (int q = 0; q < Q; ++q) {
             psi[q] = acc;

@@ -1,6 +1,7 @@
 // ofdm_devtest.hip — test-only launchers for device primitives that no C-ABI
 // entry reaches with chosen arguments: atan2_fast / cp_phase (ofdm_fft.hpp),
-// unwrap_scan (ofdm_syncdev.hpp), and the rx emit's fast path (ofdm_dev.hpp):
+// unwrap_scan and the pilot windows' plain and screened first maximum
+// (ofdm_syncdev.hpp), and the rx emit's fast path (ofdm_dev.hpp):
 // the threshold scan, the decision by thresholds beside decide_select, and
 // the in-wave assembly of output words; and the transforms themselves
 // (ofdm_fft.hpp's fft_block, fft_block_active and fft_regs_wave, ofdm_fft32.hpp's
@@ -60,6 +61,46 @@ int launch_unwrap(double* ph, const int* len, int nseq, long stride, hipStream_t
 {
     hipLaunchKernelGGL((unwrap_kernel<NT, WAVE>), dim3(nseq), dim3(WAVE ? 2 * NT : NT), 0, s, ph, len, stride);
     return (int)hipGetLastError();
+}
+
+// One fftshifted spectrum of S bins per workgroup, in LDS as in the decode
+// kernels, with its own borders[P + 2]: the pilot windows' first maxima of
+// |X| by window_first_max over hypot as cfo_kernel runs it (every window
+// 0..P) into plain, and by window_argmax_screened (the windows != P/2) into
+// screened; P + 1 entries each per spectrum, -1 where nothing was written.
+template <int NT>
+__global__ void __launch_bounds__(NT)
+window_argmax_kernel(const double2* __restrict__ spec_g, const int* __restrict__ borders_g, int P, int S,
+                     int* __restrict__ plain, int* __restrict__ screened)
+{
+    extern __shared__ double2 wa_lds[];
+    double2* spec = wa_lds;
+    int* wp = reinterpret_cast<int*>(spec + S);
+    int* ws = wp + P + 1;
+    const int tid = threadIdx.x, w = tid >> 6;
+    const long b = blockIdx.x;
+    const int* borders = borders_g + b * (P + 2);
+    for (int i = tid; i < S; i += NT) spec[i] = spec_g[b * S + i];
+    for (int i = tid; i <= P; i += NT) wp[i] = ws[i] = -1;
+    __syncthreads();
+    constexpr int AG = ofdm::ARGMAX_LANES;
+    for (int i0 = 0; i0 <= P; i0 += NT / AG) {
+        const int i = i0 + tid / AG, l = tid % AG;
+        const bool act = i <= P;
+        int lo = 0, hi = 0;
+        if (act) {
+            lo = borders[i];
+            hi = borders[i + 1];
+        }
+        const int bi = ofdm::window_first_max(lo, hi, l, [&](int j) { return hypot(spec[j].x, spec[j].y); });
+        if (act && l == 0) wp[i] = lo < hi ? (isnan(hypot(spec[lo].x, spec[lo].y)) ? lo : bi) : hi;
+    }
+    ofdm::window_argmax_screened<NT>(spec, borders, P, ws, tid, w);
+    __syncthreads();
+    for (int i = tid; i <= P; i += NT) {
+        plain[b * (P + 1) + i] = wp[i];
+        screened[b * (P + 1) + i] = ws[i];
+    }
 }
 
 __global__ void __launch_bounds__(256) tau_scan_kernel(int k, double* out)
@@ -458,6 +499,27 @@ int ofdm_devtest_cp_phase(const double* acc, const double* rot, double* out, lon
     if (n <= 0) return 0;
     hipLaunchKernelGGL(cp_phase_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
                        reinterpret_cast<const double2*>(acc), reinterpret_cast<const double2*>(rot), out, n);
+    return (int)hipGetLastError();
+}
+
+// The pilot windows' first maxima of nspec spectra of S bins (complex pairs)
+// with borders[P + 2] each, 0 <= borders <= S (the caller's check): by the
+// plain and by the screened helper, P + 1 ints per spectrum each, with a
+// workgroup of nt = 128 or 256 threads. -1 for another nt or a bad size.
+int ofdm_devtest_window_argmax(int nt, const double* spec, const int* borders, int P, int S, int nspec, int* plain,
+                               int* screened, hipStream_t s)
+{
+    if (nspec <= 0) return 0;
+    if (P < 1 || S < 1) return -1;
+    const size_t shm = sizeof(double2) * (size_t)S + sizeof(int) * 2 * (size_t)(P + 1);
+    if (shm > 64 * 1024) return -1;
+    const double2* sp = reinterpret_cast<const double2*>(spec);
+    if (nt == 128)
+        hipLaunchKernelGGL(window_argmax_kernel<128>, dim3(nspec), dim3(128), shm, s, sp, borders, P, S, plain, screened);
+    else if (nt == 256)
+        hipLaunchKernelGGL(window_argmax_kernel<256>, dim3(nspec), dim3(256), shm, s, sp, borders, P, S, plain, screened);
+    else
+        return -1;
     return (int)hipGetLastError();
 }
 

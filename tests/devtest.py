@@ -1,6 +1,7 @@
 """ctypes binding of c-ofdm_amd/lib/libofdm_devtest.so: test-only launchers
 for device primitives no C-ABI entry reaches with chosen arguments
-(atan2_fast, cp_phase, unwrap_scan; the FP64 and packed-FP32 transforms, the
+(atan2_fast, cp_phase, unwrap_scan, the pilot windows' first maximum; the
+FP64 and packed-FP32 transforms, the
 stream walker's T2 sums and screen rule, the FFT preamble search's window
 pass), and the longdouble DFT they are compared with. A missing library is an
 error."""
@@ -31,8 +32,9 @@ def lib():
         L.ofdm_devtest_fft32p.argtypes = [C.c_int, vp, vp, vp, vp, vp, vp, C.c_long, C.c_int, C.c_int, C.c_int,
                                           C.c_int, C.c_double, C.c_double, vp]
         L.ofdm_devtest_corr.argtypes = [C.c_int, vp, vp, vp, C.c_long, vp]
+        L.ofdm_devtest_window_argmax.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
         for f in (L.ofdm_devtest_atan2, L.ofdm_devtest_cp_phase, L.ofdm_devtest_unwrap, L.ofdm_devtest_fft64,
-                  L.ofdm_devtest_fft32p, L.ofdm_devtest_corr):
+                  L.ofdm_devtest_fft32p, L.ofdm_devtest_corr, L.ofdm_devtest_window_argmax):
             f.restype = C.c_int
         _lib = L
     return _lib
@@ -99,6 +101,57 @@ def unwrap_serial(ph) -> np.ndarray:
         elif d < -pi:
             ph[i] += two_pi
     return ph
+
+
+# ---------------------------------------------------------------- pilot windows
+def window_argmax(nt: int, spec, borders):
+    """The first maxima of |spec| in the windows [borders[i], borders[i+1]) of
+    every row (spec: (n, S) complex128, borders: (n, P + 2) ints within 0..S)
+    with a workgroup of nt threads per row. Returns (plain, screened), int32
+    (n, P + 1): window_first_max over hypot on every window, and
+    window_argmax_screened, which leaves window P/2 alone (-1)."""
+    import torch
+    spec = np.ascontiguousarray(spec, np.complex128)
+    borders = np.ascontiguousarray(borders, np.int32)
+    n, S = spec.shape
+    P = borders.shape[1] - 2
+    assert borders.shape[0] == n and P >= 1 and borders.min() >= 0 and borders.max() <= S
+    d, db = _dev(spec), _dev(borders)
+    plain = torch.empty((n, P + 1), dtype=torch.int32, device="cuda")
+    scr = torch.empty((n, P + 1), dtype=torch.int32, device="cuda")
+    _check(lib().ofdm_devtest_window_argmax(nt, d.data_ptr(), db.data_ptr(), P, S, n, plain.data_ptr(),
+                                            scr.data_ptr(), None), "window_argmax")
+    torch.cuda.synchronize()
+    return plain.cpu().numpy(), scr.cpu().numpy()
+
+
+def window_first_max_model(spec, borders) -> np.ndarray:
+    """std::max_element of np.hypot over each window of one spectrum: the first
+    maximum; a NaN first element is kept, later NaNs never win; an empty window
+    gives its end."""
+    mag = np.hypot(np.real(spec), np.imag(spec))
+    out = np.empty(len(borders) - 1, np.int32)
+    for i, (lo, hi) in enumerate(zip(borders[:-1], borders[1:])):
+        if lo >= hi:
+            out[i] = hi
+        elif np.isnan(mag[lo]):
+            out[i] = lo
+        else:
+            out[i] = lo + int(np.argmax(np.where(np.isnan(mag[lo:hi]), -1.0, mag[lo:hi])))
+    return out
+
+
+def window_first_max_serial(spec, borders) -> np.ndarray:
+    """The same by max_element's own loop, one comparison per element."""
+    mag = np.hypot(np.real(spec), np.imag(spec))
+    out = np.empty(len(borders) - 1, np.int32)
+    for i, (lo, hi) in enumerate(zip(borders[:-1], borders[1:])):
+        best = lo if lo < hi else hi
+        for j in range(lo + 1, hi):
+            if mag[best] < mag[j]:
+                best = j
+        out[i] = best
+    return out
 
 
 # ---------------------------------------------------------------- transforms

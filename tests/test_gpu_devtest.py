@@ -1,5 +1,6 @@
-"""The two device primitives of chan_char_lq's phase path, called directly
-through the test-only library (c-ofdm_amd/devtest, tests/devtest.py):
+"""The two device primitives of chan_char_lq's phase path and the pilot
+windows' first maximum of pilot_freq_sinh, called directly through the
+test-only library (c-ofdm_amd/devtest, tests/devtest.py):
 
 atan2_fast against mpmath.atan2 at 60 digits rounded to double, within the 3
 ulp the header claims, over arguments chosen one at a time (huge, tiny and
@@ -9,7 +10,11 @@ sign combination, the IEEE special cases); cp_phase's all-zero sums.
 unwrap_scan<NT, WAVE> against the serial one-pass loop in float64, bit for
 bit, for every instantiated form and lengths around the thread, wave and
 R-entries-per-thread boundaries, on inputs that make the scan's maps
-non-trivial: exact +-pi ties included, which no sample-level input produces."""
+non-trivial: exact +-pi ties included, which no sample-level input produces.
+
+window_argmax_screened against window_first_max over hypot, and that against
+std::max_element of np.hypot, on the inputs that reach the screened form's
+fallback (ties, non-finite elements, empty windows)."""
 from fractions import Fraction
 
 import mpmath
@@ -300,3 +305,79 @@ def test_unwrap_scan_adjustments_only_at_thread_and_wave_boundaries(nt, wave):
                     seqs.append(s)
     assert hits > 0
     _check_bits(nt, wave, seqs)
+
+
+# ---------------------------------------------------------------- pilot windows
+WINDOW_SHAPES = [(640, 2, 128), (640, 8, 128), (640, 64, 128), (1280, 64, 256)]  # S, P, threads
+
+
+def _window_cases(S, P, rng):
+    """[(name, spectrum, borders, exact)]: every window of a spectrum gets the
+    same treatment over a Gaussian floor of |z| ~ 0.35. exact: the order of the
+    window's magnitudes does not hang on hypot's last bit."""
+    wd = S // (P + 2)
+    even = (S - (P + 1) * wd) // 2 + wd * np.arange(P + 2)
+    assert wd >= 5 and even[0] >= 0 and even[-1] <= S
+
+    def floor():
+        return 0.25 * (rng.standard_normal(S) + 1j * rng.standard_normal(S))
+
+    def spots(n, first=0):  # n distinct positions in every window (from its entry `first` on), ascending
+        return [np.sort(rng.choice(np.arange(lo + first, hi), n, replace=False))
+                for lo, hi in zip(even[:-1], even[1:])]
+
+    cases = [("gauss", floor(), even, True)]
+    # four different points of equal and exact hypot (5 * 2^3) and equal |z|^2
+    z, tie = floor(), spots(4)
+    for pos in tie:
+        z[pos] = 8.0 * rng.permutation(np.array([3 + 4j, 4 + 3j, 5 + 0j, 0 + 5j]))
+    cases.append(("tie", z, even, True))
+    # |z|^2 = 64 and, later in the window, 64 (1 + 2^-52): the larger |z|^2
+    # comes second, and hypot rounds both to 8
+    z = floor()
+    for pos in spots(2):
+        z[pos] = [8.0, complex(8.0, 8.0 * 2.0 ** -26)]
+    cases.append(("last place", z, even, False))
+    z = floor()
+    for k, pos in enumerate(spots(1)):
+        z[pos] = complex(np.inf, 1.0) if k % 2 else complex(1.0, -np.inf)
+    cases.append(("inf", z, even, True))
+    z = floor()
+    z[even[:-1]] = complex(np.nan, 0.0)
+    cases.append(("nan first", z, even, True))
+    z = floor()
+    for pos in spots(3, first=1):
+        z[pos] = complex(0.0, np.nan)
+    cases.append(("nan elsewhere", z, even, True))
+    # every third window empty (lo == hi), the others wider
+    widths = np.where(np.arange(P + 1) % 3 == 1, 0, wd)
+    gaps = np.concatenate([[even[0]], even[0] + np.cumsum(widths)])
+    cases.append(("empty", floor(), gaps, True))
+    return cases, tie
+
+
+def test_window_first_max_plain_and_screened():
+    """window_argmax_screened (the CFO of every stream frame) equals
+    window_first_max over hypot in every window it decides, on Gaussian
+    spectra and on the inputs that send it to its fallback: exact ties of
+    different points, |X|^2 one place apart under equal hypot, inf, NaN as a
+    window's first element and elsewhere, empty windows; one wave and two
+    (P = 64: a second pass of the window loop at 128 threads), 128 and 256
+    threads. The plain form equals std::max_element of np.hypot wherever the
+    order does not hang on hypot's last bit; that model is first checked
+    against max_element's own loop on the CPU."""
+    rng = np.random.default_rng(20261021)
+    for S, P, nt in WINDOW_SHAPES:
+        cases, tie = _window_cases(S, P, rng)
+        models = [devtest.window_first_max_model(z, b) for _, z, b, _ in cases]
+        for (name, z, b, _), m in zip(cases, models):
+            assert np.array_equal(m, devtest.window_first_max_serial(z, b)), (S, P, name)
+        assert np.array_equal(models[1], [pos[0] for pos in tie])  # the first of the four in index order
+        plain, scr = devtest.window_argmax(nt, np.stack([z for _, z, _, _ in cases]),
+                                           np.stack([b for _, _, b, _ in cases]))
+        decided = np.arange(P + 1) != P // 2
+        for c, (name, _, _, exact) in enumerate(cases):
+            assert np.array_equal(scr[c, decided], plain[c, decided]), (S, P, nt, name)
+            assert scr[c, P // 2] == -1, (S, P, nt, name)
+            if exact:
+                assert np.array_equal(plain[c], models[c]), (S, P, nt, name)
