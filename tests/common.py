@@ -67,6 +67,23 @@ def rel_err(a, b) -> float:
     return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
 
 
+def assert_int16_match(got16, ref_iq, mult):
+    """int16 wire samples (FRAME_FORM::get_int16 = trunc(x*mult)) must be
+    identical, except where x*mult lies within 1e-9 of an integer: there the
+    truncation is decided by FFT rounding order (FFTW, oracle and GPU all
+    differ in the last ulp) and a 1-LSB difference is allowed."""
+    v = np.empty(2 * ref_iq.size)
+    v[0::2] = ref_iq.real.ravel() * mult
+    v[1::2] = ref_iq.imag.ravel() * mult
+    got = got16.ravel().astype(np.int64)
+    want = np.trunc(v).astype(np.int64)
+    diff = got != want
+    ambiguous = np.abs(v - np.round(v)) < 1e-9 * np.maximum(1.0, np.abs(v))
+    assert np.all(ambiguous[diff]), f"{int((diff & ~ambiguous).sum())} non-ambiguous int16 mismatches"
+    assert np.all(np.abs(got - want)[diff] <= 1)
+    return int(diff.sum())
+
+
 def impaired_stream(cfg, nf, seed, snr_db=20.0, cfo_max=0.004, gap_max=4096):
     """Config-4 stream: full frames (T2+preamble+message) with random 0..gap_max
     zero gaps, per-frame CFO U(-cfo_max, cfo_max) and phase, AWGN over all."""

@@ -1,8 +1,10 @@
 """Fixtures of the batched rx's geometry tests (tests/test_gpu_rx_geometry.py:
-ofdm_rx_demod, ofdm_rx_demod_i16, ofdm_rx_demod_read, ofdm_rx_demod_soft and
-ofdm_tx_modulate on every non-stream kernel instance and on geometries off the
-D = N/2 diagonal; the fixtures themselves are checked on the CPU in
-tests/test_rx_geometry_cases.py). No torch, no GPU: numpy and the oracle.
+ofdm_rx_demod, ofdm_rx_demod_i16, ofdm_rx_demod_read and ofdm_rx_demod_soft
+on every non-stream rx kernel instance and on geometries off the D = N/2
+diagonal, and one noise-free ofdm_tx_modulate with the int16 output per
+geometry; tx's other instances and branches are tests/tx_cases.py's. The
+fixtures themselves are checked on the CPU in tests/test_rx_geometry_cases.py).
+No torch, no GPU: numpy and the oracle.
 
 - CASES: the geometry table, overrides of O.DEFAULT. Per FFT size one case
   that fits the register window (S <= 8) and one that is staged (S > 8); the

@@ -31,9 +31,8 @@ import pytest
 import fec_model as F
 import oracle as O
 import soft_model as SM
-from common import ALL_CONFIGS, G, golden, payload, rel_err
+from common import ALL_CONFIGS, G, assert_int16_match, golden, payload, rel_err
 from test_gpu_decision_boundary import smith_div
-from test_gpu_parity import assert_int16_match
 from test_gpu_sync import _impaired_frames
 
 pytestmark = pytest.mark.gpu

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 import oracle as O
-from common import ALL_CONFIGS, B, CC, G, golden, payload, rel_err
+from common import ALL_CONFIGS, B, CC, G, assert_int16_match, golden, payload, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -31,23 +31,6 @@ def modem(name_or_cfg):
 
 def dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def assert_int16_match(got16, ref_iq, mult):
-    """int16 wire samples (FRAME_FORM::get_int16 = trunc(x*mult)) must be
-    identical, except where x*mult lies within 1e-9 of an integer: there the
-    truncation is decided by FFT rounding order (FFTW, oracle and GPU all
-    differ in the last ulp) and a 1-LSB difference is allowed."""
-    v = np.empty(2 * ref_iq.size)
-    v[0::2] = ref_iq.real.ravel() * mult
-    v[1::2] = ref_iq.imag.ravel() * mult
-    got = got16.ravel().astype(np.int64)
-    want = np.trunc(v).astype(np.int64)
-    diff = got != want
-    ambiguous = np.abs(v - np.round(v)) < 1e-9 * np.maximum(1.0, np.abs(v))
-    assert np.all(ambiguous[diff]), f"{int((diff & ~ambiguous).sum())} non-ambiguous int16 mismatches"
-    assert np.all(np.abs(got - want)[diff] <= 1)
-    return int(diff.sum())
 
 
 def host(t):

@@ -42,8 +42,8 @@ import pytest
 
 import oracle as O
 import rx_geometry_cases as RG
-from common import rel_err
-from test_gpu_parity import TOL, assert_int16_match
+from common import assert_int16_match, rel_err
+from test_gpu_parity import TOL
 from test_gpu_soft import FMTS, check_against_oracle, llr_buffer, take_llr
 
 pytestmark = pytest.mark.gpu

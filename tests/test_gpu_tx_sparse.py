@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 import oracle as O
-from common import B, CC, D, cfg, payload, rel_err
+from common import B, CC, D, assert_int16_match, cfg, payload, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -46,19 +46,6 @@ def dev(a):
 def host(t):
     torch.cuda.synchronize()
     return t.cpu().numpy()
-
-
-def assert_int16_match(got16, ref_iq, mult):
-    """trunc(x * mult) per component, identical except where x * mult lies
-    within 1e-9 of an integer (the rule of test_gpu_parity)."""
-    v = np.empty(2 * ref_iq.size)
-    v[0::2] = ref_iq.real.ravel() * mult
-    v[1::2] = ref_iq.imag.ravel() * mult
-    got = got16.ravel().astype(np.int64)
-    want = np.trunc(v).astype(np.int64)
-    diff = got != want
-    ambiguous = np.abs(v - np.round(v)) < 1e-9 * np.maximum(1.0, np.abs(v))
-    assert np.all(ambiguous[diff]) and np.all(np.abs(got - want)[diff] <= 1)
 
 
 def both_ways(m, run):
