@@ -449,8 +449,9 @@ __global__ void __launch_bounds__((1 << LOGN) / 8, tx_min_blocks(LOGN, I16)) tx_
 // thread, coalesced) while symbol s is transformed; the FFT ping-pongs
 // between two LDS images (fft_pp: one barrier per pass, no input stage).
 // STAGED=false: the frame's S*D equalisation inputs live in VGPRs
-//   (S <= RX_SMAX, D <= RX_DPT*T), written through a wave-uniform switch on
-//   the symbol index so every register index is compile-time.
+//   (S <= RX_SMAX, D <= RX_DPT*T), written by straight-line symbol steps
+//   (left at the first s >= S) and read through a wave-uniform switch on the
+//   symbol index, so every register index is compile-time.
 // STAGED=true: any S; inputs parked in a.ystage (same-thread re-read).
 // The next symbol's 8 samples per thread, held in registers across the FFT:
 // complex<double> (4 VGPRs each) or, for wire-format input, complex<int16>

@@ -113,21 +113,27 @@
         // previous epilogue ended with a barrier)
         double2* first = bufA;
         double2* second = bufB;
-#pragma unroll 1
-        for (int s = 0; s < S; ++s) {
+        // One symbol step. With the register window (!STAGED) the steps are
+        // straight-line code, s and the window row W compile-time: the put's
+        // LDS reads land in the window's own registers, and the allocator
+        // has no rolled loop to split the window's live range around (it
+        // copied half the window per symbol in each direction). STAGED keeps
+        // one rolled step (W = 0 names no register there).
+        auto step = [&](int s, auto wc) __attribute__((always_inline)) {
+            constexpr int W = decltype(wc)::value;
             double2 v[8];
             if (s == 0) {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's DMA of symbol 0 landed
 #pragma unroll
                 for (int i = 0; i < 8; ++i) v[i] = stage_get<LOGN, I16>(bufB, t + T * i);
+                // the reads stay in this branch: in the rolled step they were
+                // merged with pf.get's below into loads through a select of
+                // the two pointers, which kept pf in scratch memory
+                asm volatile("" ::: "memory");
             } else {
 #pragma unroll
                 for (int i = 0; i < 8; ++i) v[i] = pf.get(i);
             }
-            // SYNC: the phase ramp is applied before the next symbol's
-            // prefetch is issued, so its sincos temporaries are not live
-            // beside the 8 prefetch registers (which spilled at N = 512)
-            if (!SYNC && s + 1 < S) pf.load(a, x0 + (long)(s + 1) * L, t);
             if constexpr (SYNC) {
                 // sample m = t + T*i of the body: *= e^{i(A + B m)}, by a
                 // running product from e^{i(A + B t)} in steps of e^{i B T};
@@ -147,15 +153,23 @@
                     v[i] = cmul(v[i], c);
                     if (i < 7) c = cmul(c, w);
                 }
-                asm volatile("" ::: "memory");  // keep the prefetch below the ramp
-                if (s + 1 < S) pf.load(a, x0 + (long)(s + 1) * L, t);
             }
             // opaque copy of t: the per-pass LDS addresses are recomputed each
             // symbol instead of being hoisted out of the loop and held live
             // beside the register window
             int tl;
             asm volatile("v_mov_b32 %0, %1" : "=v"(tl) : "v"(t));
-            double2* res = fft_pp<LOGN, -1>(v, tl, lds_tw, first, second);
+            // fft_pp in two parts, the next symbol's prefetch issued between
+            // them: pass 0 reads the prefetch registers themselves (no copy
+            // into the transform's registers), and they are free to be
+            // reloaded once it has written to LDS. SYNC: the phase ramp's
+            // sincos temporaries are dead by then as well (live beside the 8
+            // prefetch registers, they spilled at N = 512).
+            stockham_pass<LOGN, 8, 1, -1>(v, tl, lds_tw, first);
+            asm volatile("" ::: "memory");  // keep the prefetch below pass 0
+            if (s + 1 < S) pf.load(a, x0 + (long)(s + 1) * L, t);
+            fft_pp_tail<LOGN, 1, -1>(v, tl, lds_tw, second, first, NoHook());
+            double2* res = (FftPasses<LOGN>::value & 1) ? first : second;
             first = res == bufA ? bufB : bufA;
             second = res;
             if (t < P) pil[s * P + t] = res[pbin];
@@ -166,19 +180,23 @@
                     if (d < D) a.ystage[(f * S + s) * D + d] = res[pk[i] & 0xffff];
                 }
             } else {
-                switch (s) {
-#define OFDM_RX_PUT(W)                                                                    \
-    case W:                                                                               \
-        if constexpr (W < SW) {                                                           \
-            _Pragma("unroll") for (int i = 0; i < RX_DPT; ++i) y[W][i] = res[pk[i] & 0xffff]; \
-        }                                                                                 \
-        break;
-                    OFDM_RX_PUT(0) OFDM_RX_PUT(1) OFDM_RX_PUT(2) OFDM_RX_PUT(3)
-                    OFDM_RX_PUT(4) OFDM_RX_PUT(5) OFDM_RX_PUT(6) OFDM_RX_PUT(7)
-#undef OFDM_RX_PUT
-                    default: break;
-                }
+#pragma unroll
+                for (int i = 0; i < RX_DPT; ++i) y[W][i] = res[pk[i] & 0xffff];
             }
+        };
+        if constexpr (STAGED) {
+#pragma unroll 1
+            for (int s = 0; s < S; ++s) step(s, std::integral_constant<int, 0>{});
+        } else {
+            do {  // steps 0 .. RX_SMAX-1, left at the first s >= S (uniform)
+#define OFDM_RX_STEP(W) \
+    if (W >= S) break;  \
+    step(W, std::integral_constant<int, W>{});
+                OFDM_RX_STEP(0) OFDM_RX_STEP(1) OFDM_RX_STEP(2) OFDM_RX_STEP(3)
+                OFDM_RX_STEP(4) OFDM_RX_STEP(5) OFDM_RX_STEP(6) OFDM_RX_STEP(7)
+#undef OFDM_RX_STEP
+            } while (false);
+            static_assert(RX_SMAX == 8, "one OFDM_RX_STEP per window row");
         }
         lds_barrier();  // pilots of the last symbol visible; every thread is done reading bufB
         OFDM_PHASE(rx_phys_gains);
