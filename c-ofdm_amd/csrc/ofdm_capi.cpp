@@ -38,6 +38,7 @@ static constexpr int kRcclInt64 = 4, kRcclSum = 0;  // rccl.h: ncclInt64, ncclSu
 #include "ofdm_csi.hpp"
 #include "ofdm_ctx.hpp"
 #include "ofdm_internal.hpp"
+#include "ofdm_mac.hpp"
 #include "ofdm_sync.hpp"
 
 namespace {
@@ -1258,6 +1259,108 @@ int ofdm_scramble(ofdm_ctx* c, const uint8_t* in, size_t in_stride, size_t ncw, 
     ofdm::ScrArgs a{in, out, seeds, (long)in_stride, (long)out_stride, (long)ncw, (long)nbits, seed};
     hipError_t e = ofdm::launch_scramble(a, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "scramble launch");
+    return OFDM_OK;
+}
+
+// ---- MAC framing and frame check
+// The argument rules the two batched calls share; *cap receives the payload capacity.
+static int mac_sizes_check(size_t frame_len, int fcs, size_t frame_stride, size_t nframes, size_t* cap)
+{
+    if (fcs != OFDM_FCS_NONE && fcs != OFDM_FCS_CRC32) return fail(OFDM_ERR_INVALID, "fcs is not OFDM_FCS_NONE / OFDM_FCS_CRC32");
+    const size_t f = fcs == OFDM_FCS_CRC32 ? 4 : 0;
+    if (frame_len < ofdm::MAC_HDR + f || frame_len > ofdm::MAC_MAX_FRAME)
+        return fail(OFDM_ERR_INVALID, "frame_len %zu is not in [%zu, %u]", frame_len, ofdm::MAC_HDR + f, ofdm::MAC_MAX_FRAME);
+    if (frame_stride < frame_len) return fail(OFDM_ERR_INVALID, "frame_stride below frame_len");
+    if (nframes > (size_t)LONG_MAX / frame_stride) return fail(OFDM_ERR_INVALID, "nframes out of range");
+    *cap = frame_len - ofdm::MAC_HDR - f;
+    return OFDM_OK;
+}
+
+static bool mac_overlap(const void* a, size_t na, const void* b, size_t nb)
+{
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return na && nb && a0 < b0 + nb && b0 < a0 + na;
+}
+
+int ofdm_mac_payload_len(size_t frame_len, int fcs, size_t* cap)
+{
+    if (!cap) return fail(OFDM_ERR_INVALID, "null argument");
+    size_t v = 0;
+    if (int rc = mac_sizes_check(frame_len, fcs, frame_len, 1, &v)) return rc;
+    *cap = v;
+    return OFDM_OK;
+}
+
+// (the context is asked for last: the argument rules hold without a device)
+int ofdm_mac_write(ofdm_ctx* c, const uint8_t* payload, size_t payload_stride, size_t payload_len, size_t nframes,
+                   size_t frame_len, int fcs, unsigned tx_id, unsigned rx_id, unsigned seq0, const uint16_t* seqs,
+                   uint8_t* frames_out, size_t frame_stride, void* stream)
+{
+    size_t cap = 0;
+    if (int rc = mac_sizes_check(frame_len, fcs, frame_stride, nframes, &cap)) return rc;
+    if (payload_len > cap) return fail(OFDM_ERR_INVALID, "payload_len %zu above the frame's %zu", payload_len, cap);
+    if (payload_stride < payload_len) return fail(OFDM_ERR_INVALID, "payload_stride below payload_len");
+    if (payload_stride && nframes > (size_t)LONG_MAX / payload_stride) return fail(OFDM_ERR_INVALID, "nframes out of range");
+    if (tx_id > 65535 || rx_id > 65535 || seq0 > 65535) return fail(OFDM_ERR_INVALID, "tx_id, rx_id and seq0 are 16-bit values");
+    if (seqs && ((uintptr_t)seqs & 1)) return fail(OFDM_ERR_INVALID, "seqs must be 2-byte aligned");
+    if (!frames_out || (!payload && payload_len)) return fail(OFDM_ERR_INVALID, "null argument");
+    if (nframes && mac_overlap(payload, (nframes - 1) * payload_stride + payload_len, frames_out, nframes * frame_stride))
+        return fail(OFDM_ERR_INVALID, "payload and frames_out overlap");
+    if (!c) return fail(OFDM_ERR_INVALID, "null context");
+    if (nframes == 0) return OFDM_OK;
+    ofdm::MacWriteArgs a{};
+    a.payload = payload;
+    a.frames = frames_out;
+    a.seqs = seqs;
+    a.payload_stride = payload_stride;
+    a.frame_stride = frame_stride;
+    a.nframes = nframes;
+    a.payload_len = (unsigned)payload_len;
+    a.frame_len = (unsigned)frame_len;
+    a.m = (unsigned)(cap + ofdm::MAC_HDR);
+    a.tx_id = tx_id;
+    a.rx_id = rx_id;
+    a.seq0 = seq0;
+    hipError_t e = ofdm::launch_mac_write(a, fcs == OFDM_FCS_CRC32, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "mac write launch");
+    return OFDM_OK;
+}
+
+int ofdm_mac_read(ofdm_ctx* c, const uint8_t* frames, size_t frame_stride, size_t nframes, size_t frame_len, int fcs,
+                  int expect_rx_id, uint8_t* payload_out, size_t payload_stride, ofdm_mac_info* info_out,
+                  unsigned long long* frame_errors, void* stream)
+{
+    size_t cap = 0;
+    if (int rc = mac_sizes_check(frame_len, fcs, frame_stride, nframes, &cap)) return rc;
+    if (expect_rx_id > 65535) return fail(OFDM_ERR_INVALID, "expect_rx_id is a 16-bit value, or negative for any");
+    if (payload_out && payload_stride < cap) return fail(OFDM_ERR_INVALID, "payload_stride below the frame's %zu payload bytes", cap);
+    if (payload_out && payload_stride && nframes > (size_t)LONG_MAX / payload_stride)
+        return fail(OFDM_ERR_INVALID, "nframes out of range");
+    if (info_out && !aligned16(info_out)) return fail(OFDM_ERR_INVALID, "info_out must be 16-byte aligned");
+    if (frame_errors && ((uintptr_t)frame_errors & 7)) return fail(OFDM_ERR_INVALID, "frame_errors must be 8-byte aligned");
+    if (!frames || (!payload_out && !info_out && !frame_errors)) return fail(OFDM_ERR_INVALID, "null argument");
+    if (nframes) {
+        const size_t in_bytes = (nframes - 1) * frame_stride + frame_len;
+        if ((payload_out && mac_overlap(frames, in_bytes, payload_out, (nframes - 1) * payload_stride + cap)) ||
+            (info_out && mac_overlap(frames, in_bytes, info_out, nframes * sizeof(ofdm_mac_info))) ||
+            (frame_errors && mac_overlap(frames, in_bytes, frame_errors, 8)))
+            return fail(OFDM_ERR_INVALID, "frames and an output overlap");
+    }
+    if (!c) return fail(OFDM_ERR_INVALID, "null context");
+    if (nframes == 0) return OFDM_OK;
+    ofdm::MacReadArgs a{};
+    a.frames = frames;
+    a.payload = payload_out;
+    a.info = reinterpret_cast<ofdm::MacU4*>(info_out);
+    a.frame_errors = frame_errors;
+    a.frame_stride = frame_stride;
+    a.payload_stride = payload_out ? payload_stride : 0;
+    a.nframes = nframes;
+    a.frame_len = (unsigned)frame_len;
+    a.m = (unsigned)(cap + ofdm::MAC_HDR);
+    a.expect_rx_id = expect_rx_id;
+    hipError_t e = ofdm::launch_mac_read(a, fcs == OFDM_FCS_CRC32, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "mac read launch");
     return OFDM_OK;
 }
 

@@ -29,7 +29,17 @@ ERRORS = {-1: "INVALID", -2: "UNSUPPORTED", -3: "HIP", -4: "IO", -5: "NOMEM", -6
 LLR_F32, LLR_I8 = 0, 1  # OFDM_LLR_*: soft-decision output formats
 FEC_R12, FEC_R23, FEC_R34 = 0, 1, 2  # OFDM_FEC_*: channel-code rates
 IL_FORWARD, IL_INVERSE = 0, 1  # OFDM_IL_*: interleaver directions
+FCS_NONE, FCS_CRC32 = 0, 1  # OFDM_FCS_*: frame check sequence of a MAC frame
 SYNC_CFO, SYNC_FREQ_SHIFT, SYNC_CP, SYNC_PHASE, SYNC_CHAN, SYNC_ALL = 1, 2, 4, 8, 16, 31
+# ofdm_mac_info as a numpy structured dtype (16 bytes): view ofdm_mac_read's
+# info_out, a uint8 tensor of 16 bytes per frame, through it
+MAC_INFO_FIELDS = [("tx_id", "<u2"), ("rx_id", "<u2"), ("seq_num", "<u2"), ("cs", "<u2"), ("cs_calc", "<u2"),
+                   ("cs_ok", "u1"), ("fcs_ok", "u1"), ("ok", "u1"), ("reserved", "u1", (3,))]
+
+
+def mac_info_dtype():
+    import numpy as np
+    return np.dtype(MAC_INFO_FIELDS)
 
 
 class Params(C.Structure):
@@ -118,6 +128,9 @@ SIGNATURES = {
     "ofdm_interleave_bits": (_I, [_V, _V, _SZ, _SZ, _SZ, _SZ, _I, _V, _V]),
     "ofdm_interleave_llr": (_I, [_V, _V, _I, _SZ, _SZ, _SZ, _SZ, _I, _V, _V]),
     "ofdm_scramble": (_I, [_V, _V, _SZ, _SZ, _SZ, C.c_uint, _V, _V, _SZ, _V]),
+    "ofdm_mac_payload_len": (_I, [_SZ, _I, C.POINTER(_SZ)]),
+    "ofdm_mac_write": (_I, [_V, _V, _SZ, _SZ, _SZ, _SZ, _I, C.c_uint, C.c_uint, C.c_uint, _V, _V, _SZ, _V]),
+    "ofdm_mac_read": (_I, [_V, _V, _SZ, _SZ, _SZ, _I, _I, _V, _SZ, _V, _V, _V]),
     "ofdm_map": (_I, [_V, _V, _SZ, _V, _V]),
     "ofdm_fft_write": (_I, [_V, _V, _SZ, _V, _V]),
     "ofdm_fft_read": (_I, [_V, _V, _SZ, _V, _V]),
@@ -231,6 +244,14 @@ def fec_workspace_size(ncw: int, info_bits: int) -> int:
     """ofdm_fec_workspace_size: bytes of survivor storage fec_decode wants."""
     n = C.c_size_t()
     check(lib().ofdm_fec_workspace_size(ncw, info_bits, C.byref(n)))
+    return n.value
+
+
+def mac_payload_len(frame_len: int, fcs: int = FCS_CRC32) -> int:
+    """ofdm_mac_payload_len: payload bytes of a MAC frame of frame_len bytes
+    (host arithmetic)."""
+    n = C.c_size_t()
+    check(lib().ofdm_mac_payload_len(frame_len, fcs, C.byref(n)))
     return n.value
 
 
@@ -453,6 +474,35 @@ class Modem:
         check(lib().ofdm_scramble(self.h, _ptr(data), nbytes if in_stride is None else in_stride, ncw, nbits, seed,
                                   _ptr(seeds), _ptr(out), nbytes if out_stride is None else out_stride,
                                   _stream(stream)))
+
+    # ---- MAC framing and frame check
+    mac_payload_len = staticmethod(mac_payload_len)
+
+    def mac_write(self, payload, payload_len: int, nframes: int, frame_len: int, frames_out, fcs: int = FCS_CRC32,
+                  tx_id: int = 0, rx_id: int = 0, seq0: int = 0, seqs=None, payload_stride: int | None = None,
+                  frame_stride: int | None = None, stream=None):
+        """ofdm_mac_write: nframes MAC frames (header, checksum, payload_len
+        payload bytes zero-filled to the frame's capacity, FCS) of frame_len
+        bytes, frame_stride bytes written per frame; uint8 tensors, strides in
+        bytes and minimal by default; `seqs`: a device uint16/int16 tensor of
+        sequence numbers instead of seq0 + f."""
+        check(lib().ofdm_mac_write(self.h, _ptr(payload), payload_len if payload_stride is None else payload_stride,
+                                   payload_len, nframes, frame_len, fcs, tx_id, rx_id, seq0, _ptr(seqs),
+                                   _ptr(frames_out), frame_len if frame_stride is None else frame_stride,
+                                   _stream(stream)))
+
+    def mac_read(self, frames, nframes: int, frame_len: int, fcs: int = FCS_CRC32, payload_out=None, info_out=None,
+                 frame_errors=None, expect_rx_id: int = -1, frame_stride: int | None = None,
+                 payload_stride: int | None = None, stream=None):
+        """ofdm_mac_read: checks nframes frames; payload_out (uint8, the
+        frame's capacity per frame by default), info_out (16 bytes per frame,
+        16-byte aligned: mac_info_dtype()) and frame_errors (one int64 /
+        uint64 element, increased by the frames that are not ok) are each
+        optional."""
+        pstr = mac_payload_len(frame_len, fcs) if payload_stride is None else payload_stride
+        check(lib().ofdm_mac_read(self.h, _ptr(frames), frame_len if frame_stride is None else frame_stride, nframes,
+                                  frame_len, fcs, expect_rx_id, _ptr(payload_out), pstr, _ptr(info_out),
+                                  _ptr(frame_errors), _stream(stream)))
 
     def map(self, data, nbytes: int, points_out, stream=None):
         check(lib().ofdm_map(self.h, _ptr(data), nbytes, _ptr(points_out), _stream(stream)))

@@ -21,7 +21,7 @@
  *     fec_encode, fec_decode, interleave_bits, interleave_llr, scramble, fft_write, fft_read, bit_convert,
  *     int16_to_double, double_to_int16, t2_scan, find_preamble, cfo_estimate,
  *     freq_shift, cp_sync, phase_sync, sync_chain, chan_estimate, sync_frames,
- *     chan_estimate_ls, soft_demap_csi)
+ *     chan_estimate_ls, soft_demap_csi, mac_write, mac_read)
  *     and ofdm_copy only launch kernels on `stream`: no
  *     allocation, no host copy, no synchronisation, and every per-launch
  *     device counter is left as the next launch needs it. A chain of them can
@@ -453,10 +453,10 @@ int ofdm_fec_decode(ofdm_ctx* ctx, const void* llr, int fmt, size_t llr_stride, 
 
 /* ---- interleaver and scrambler: the two stages between the channel code
  * and the modem. The device-side chain is
- *     tx: ofdm_scramble, ofdm_fec_encode, ofdm_interleave_bits (forward),
- *         ofdm_tx_modulate
+ *     tx: ofdm_mac_write, ofdm_scramble, ofdm_fec_encode,
+ *         ofdm_interleave_bits (forward), ofdm_tx_modulate
  *     rx: ofdm_rx_demod_soft, ofdm_interleave_llr (inverse), ofdm_fec_decode,
- *         ofdm_scramble
+ *         ofdm_scramble, ofdm_mac_read
  * (INTEGRATION.md has the arguments). Every call below that takes a stream is
  * batched, takes device pointers and only launches kernels: no allocation,
  * no host copy, no synchronisation; capturable.
@@ -485,8 +485,8 @@ int ofdm_fec_decode(ofdm_ctx* ctx, const void* llr, int fmt, size_t llr_stride, 
  * outside 1..127, misaligned F32, in and out overlapping (ofdm_scramble: in ==
  * out with other than equal strides). nblocks == 0 or ncw == 0: OFDM_OK, no
  * launch. A grid that does not fit: OFDM_ERR_HIP, nothing launched.
- * Not covered: the deinterleave fused into the decoder or the soft rx, a CRC,
- * the per-carrier weight of ofdm_soft_demap_csi fused into ofdm_rx_demod_soft,
+ * Not covered: the deinterleave fused into the decoder or the soft rx (the
+ * frame check is ofdm_mac_read, below), the per-carrier weight of ofdm_soft_demap_csi fused into ofdm_rx_demod_soft,
  * a noise-variance estimate, MMSE equalisation, and the compat layer. */
 enum { OFDM_IL_FORWARD = 0, OFDM_IL_INVERSE = 1 };
 
@@ -519,6 +519,80 @@ int ofdm_interleave_llr(ofdm_ctx* ctx, const void* in, int fmt, size_t nblocks, 
  * ((v-1) mod 127) + 1. in == out with equal strides is allowed. */
 int ofdm_scramble(ofdm_ctx* ctx, const uint8_t* in, size_t in_stride, size_t ncw, size_t nbits,
                   unsigned seed, const uint8_t* seeds, uint8_t* out, size_t out_stride, void* stream);
+
+/* ---- MAC framing and frame check: the reference's outermost layer,
+ * mac.write(...) before FRAME_FORM::write (main.cpp:37, tx.cpp:34) and
+ * mac.read(...) after Modulation::demod (main.cpp:82, rx.cpp:221), batched on
+ * the device, with the frame check sequence a coded link needs. A MAC frame is
+ * frame_len bytes, F = 4 with OFDM_FCS_CRC32 and 0 with OFDM_FCS_NONE:
+ *     0 .. 7                        tx_id, rx_id, seq_num, cs: four uint16,
+ *                                   little-endian (the reference's MAC header)
+ *     8 .. frame_len-F-1            payload, cap = frame_len - 8 - F bytes; a
+ *                                   shorter input is zero-filled (MAC::write)
+ *     frame_len-F .. frame_len-1    FCS (OFDM_FCS_CRC32 only)
+ * cs is the sum of bytes [0, frame_len-F) without bytes 6 and 7, mod 2^16
+ * (MAC::calc_cs; 0x577E on the golden frame). With OFDM_FCS_NONE the frame is
+ * bit for bit MAC(tx, rx, frame_len).write(payload, seq). The FCS is
+ * CRC-32/IEEE 802.3 (reflected polynomial 0xEDB88320, initial value and final
+ * XOR 0xFFFFFFFF: zlib's crc32) of bytes [0, frame_len-4) with cs in place,
+ * stored little-endian as the 802.11 FCS is: the CRC-32 of a whole good frame
+ * is the residue 0x2144DF1C. Valid: 8 + F <= frame_len <= 65536,
+ * payload_len <= cap.
+ *
+ * The two batched calls take device pointers and only launch one kernel: no
+ * allocation, no host copy, no synchronisation; capturable. One wave works on
+ * a frame, 16 bytes per lane where both buffers and both strides are 4-byte
+ * aligned (fastest 16-byte aligned), a byte per lane otherwise.
+ *
+ * OFDM_ERR_INVALID: null required pointers, unknown fcs, sizes outside the
+ * rules above, strides below the length they carry, ids above 65535, input
+ * and output overlapping, a misaligned info_out (16 bytes), frame_errors (8)
+ * or seqs (2). These are checked before the context is, and before any device
+ * call. nframes == 0: OFDM_OK, no launch. The grid is bounded (the waves
+ * stride over the frames), so no launch is too large for it.
+ * Not covered: other polynomials, a CRC fused into the decoder or the
+ * descrambler, fragmentation, ARQ, addressing beyond the rx_id filter, and the
+ * compat layer's MAC class, which stays the host class it is. */
+enum { OFDM_FCS_NONE = 0, OFDM_FCS_CRC32 = 1 };
+
+/* ofdm_mac_read's verdict on one frame: 16 bytes, the array 16-byte aligned. */
+typedef struct ofdm_mac_info {
+    uint16_t tx_id, rx_id, seq_num, cs;   /* as received */
+    uint16_t cs_calc;                     /* recomputed */
+    uint8_t  cs_ok, fcs_ok;               /* fcs_ok = 1 with OFDM_FCS_NONE */
+    uint8_t  ok;                          /* cs_ok && fcs_ok && the rx_id filter */
+    uint8_t  reserved[3];                 /* written 0 */
+} ofdm_mac_info;
+
+/* Host arithmetic: *cap = frame_len - 8 - F. OFDM_ERR_INVALID for an unknown
+ * fcs or a frame_len outside [8 + F, 65536]. */
+int ofdm_mac_payload_len(size_t frame_len, int fcs, size_t* cap);
+
+/* nframes frames from payload_len payload bytes each (payload may be NULL
+ * where payload_len is 0). Frame f carries seq_num = (seq0 + f) mod 2^16, as
+ * tx.cpp counts, or seqs[f] where seqs (nullable, device, nframes uint16) is
+ * given. Writes exactly frame_stride bytes per frame, the MAC frame and then
+ * zeros (ofdm_fec_encode's coded_stride convention): frame_stride =
+ * bytes_per_frame feeds ofdm_tx_modulate, frame_stride = ceil(info_bits/8)
+ * feeds ofdm_scramble / ofdm_fec_encode. payload and frames_out must not
+ * overlap. */
+int ofdm_mac_write(ofdm_ctx* ctx, const uint8_t* payload, size_t payload_stride, size_t payload_len,
+                   size_t nframes, size_t frame_len, int fcs, unsigned tx_id, unsigned rx_id,
+                   unsigned seq0, const uint16_t* seqs, uint8_t* frames_out, size_t frame_stride,
+                   void* stream);
+
+/* Checks nframes received frames in one pass: payload_out (nullable) receives
+ * cap bytes per frame, bad frames included, as MAC::read does; info_out
+ * (nullable) the header as received and the verdict; *frame_errors (nullable,
+ * device, 8-byte aligned) is increased atomically by the number of frames with
+ * ok == 0 and is not written where there is none. ok also requires
+ * rx_id == expect_rx_id where expect_rx_id >= 0. At least one of the three
+ * outputs must be given. The input is not modified and must not overlap an
+ * output. */
+int ofdm_mac_read(ofdm_ctx* ctx, const uint8_t* frames, size_t frame_stride, size_t nframes,
+                  size_t frame_len, int fcs, int expect_rx_id, uint8_t* payload_out,
+                  size_t payload_stride, ofdm_mac_info* info_out, unsigned long long* frame_errors,
+                  void* stream);
 
 /* Modulation::mod alone (modulation.cpp:39-50): nbytes -> nbytes*8/k points. */
 int ofdm_map(ofdm_ctx* ctx, const uint8_t* bytes, size_t nbytes, double* points_out, void* stream);
