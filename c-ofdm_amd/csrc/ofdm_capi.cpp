@@ -1,13 +1,13 @@
 // ofdm_capi.cpp — implementation of include/ofdm_mi355x.h (the C-ABI drop-in
-// boundary). Host side: config parsing, validation, the constant tables the
-// reference builds in its constructors, and kernel dispatch. Every compute
-// entry point launches HIP kernels; there is no CPU compute path.
+// boundary): the entry points. Host side: argument checks and kernel dispatch
+// on a context that ofdm_create.cpp built (config parsing, validation and the
+// constant tables are there; the stream receiver is ofdm_stream_call.cpp).
+// Every compute entry point launches HIP kernels; there is no CPU compute path.
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <climits>
-#include <cctype>
 #include <cmath>
 #include <complex>
 #include <cstdarg>
@@ -16,12 +16,9 @@
 #include <chrono>
 #include <mutex>
 #include <cstring>
-#include <fstream>
 #include <iterator>
-#include <random>
 #include <stdexcept>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "../../include/ofdm_mi355x.h"
@@ -72,58 +69,6 @@ using ofdm::grow_host;
 using ofdm::hip_fail;
 using ofdm::initial_state;
 
-namespace {
-
-int ilog2_exact(long n)
-{
-    if (n <= 0 || (n & (n - 1))) return -1;
-    int l = 0;
-    while ((1L << l) < n) ++l;
-    return l;
-}
-
-// key=value ConfigMap exactly as parse_config (config/parser.cpp:4-33):
-// trim, skip blank and '#' lines and lines without '=', strip every space
-// from key and value, std::stol the value (throws -> OFDM_ERR_PARSE).
-int parse_file(const char* path, std::unordered_map<std::string, long>& cfg)
-{
-    if (!path) return fail(OFDM_ERR_INVALID, "null config path");
-    std::ifstream file(path);
-    if (!file.is_open()) return fail(OFDM_ERR_IO, "Cannot open config file");
-    std::string line;
-    while (std::getline(file, line)) {
-        line.erase(line.begin(), std::find_if(line.begin(), line.end(),
-                                              [](unsigned char ch) { return !std::isspace(ch); }));
-        line.erase(std::find_if(line.rbegin(), line.rend(), [](unsigned char ch) { return !std::isspace(ch); })
-                       .base(),
-                   line.end());
-        if (line.empty() || line[0] == '#') continue;
-        auto pos = line.find('=');
-        if (pos == std::string::npos) continue;
-        std::string key = line.substr(0, pos), value = line.substr(pos + 1);
-        key.erase(std::remove_if(key.begin(), key.end(), ::isspace), key.end());
-        value.erase(std::remove_if(value.begin(), value.end(), ::isspace), value.end());
-        try {
-            cfg[key] = std::stol(value);
-        } catch (const std::exception& e) {
-            return fail(OFDM_ERR_PARSE, "stol failed for key '%s': %s", key.c_str(), e.what());
-        }
-    }
-    return OFDM_OK;
-}
-
-template <class T>
-int upload(T** dst, const std::vector<T>& v)
-{
-    HIP_TRY(hipMalloc((void**)dst, std::max<size_t>(1, v.size()) * sizeof(T)));
-    if (!v.empty()) HIP_TRY(hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return OFDM_OK;
-}
-
-}  // namespace
-
-using ofdm::twiddles;  // ofdm_internal.hpp
-
 // ---- the other helpers that ofdm_ctx.hpp declares ----
 
 // True while `st` is being captured into a hipGraph. Asked only on the paths
@@ -146,51 +91,6 @@ int ofdm::capture_refused(const char* what)
                                       "before the capture)", what);
 }
 
-// pilot_freq_sinh plan for a form of nsym symbols: S = (N+cp)*nsym = M or 5*M,
-// M = 2^m; window borders exactly as Frame.hpp:311-321 computes them. A new
-// form length builds and uploads its tables (allocation, host copies): `st` is
-// the stream the caller will launch on, refused while it is being captured.
-int ofdm::cfo_plan(ofdm_ctx* c, int nsym, ofdm_ctx::CfoPlan** out, hipStream_t st)
-{
-    for (auto& pl : c->cfo_plans)
-        if (pl.nsym == nsym) {
-            *out = &pl;
-            return OFDM_OK;
-        }
-    if (capturing(st)) return capture_refused("the tables of a new CFO form length");
-    const long S = (long)c->L * nsym;
-    ofdm_ctx::CfoPlan pl;
-    pl.nsym = nsym;
-    if (ilog2_exact(S) >= 6 && ilog2_exact(S) <= 12) {
-        pl.g = 1;
-        pl.logm = ilog2_exact(S);
-    } else if (S % 5 == 0 && ilog2_exact(S / 5) >= 6 && ilog2_exact(S / 5) <= 10) {
-        pl.g = 5;
-        pl.logm = ilog2_exact(S / 5);
-    } else {
-        return fail(OFDM_ERR_UNSUPPORTED, "pilot_freq_sinh: form length %ld is not 2^a or 5*2^a (64 <= 2^a <= %d)", S,
-                    4096);
-    }
-    const int P = c->P;
-    const double rel_bw = double(c->D + c->P) / (c->N);
-    const double rel_pilot_w = rel_bw / P;
-    const int pilot_w = int(S * rel_pilot_w);
-    std::vector<int> borders(P + 2);
-    for (int i = 0, j = int((1.0 - rel_bw - rel_pilot_w) / 2.0 * S); i < P + 2; i++) {
-        borders[i] = j;
-        j += pilot_w;
-    }
-    borders[0] = std::max(0, borders[0]);
-    for (int b : borders)
-        if (b < 0 || b > S) return fail(OFDM_ERR_UNSUPPORTED, "pilot_freq_sinh windows leave the spectrum");
-    int rc;
-    if ((rc = upload(&pl.tw_sub, twiddles(1 << pl.logm))) || (rc = upload(&pl.borders, borders))) return rc;
-    if (pl.g == 5 && (rc = upload(&pl.tw_full, twiddles((int)S)))) return rc;
-    c->cfo_plans.push_back(pl);
-    *out = &c->cfo_plans.back();
-    return OFDM_OK;
-}
-
 bool ofdm::aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // Device scratch that only grows (contents not preserved).
@@ -198,23 +98,21 @@ int ofdm::grow(ofdm_ctx* c, ofdm_ctx::Grow& g, size_t need)
 {
     if (need <= g.bytes) return OFDM_OK;
     HIP_TRY(hipSetDevice(c->device));
-    if (g.p) HIP_TRY(hipFree(g.p));
-    g.p = nullptr;
     g.bytes = 0;
-    HIP_TRY(hipMalloc(&g.p, need));
+    HIP_TRY(g.p.reset());
+    HIP_TRY(hipMalloc(g.p.put(), need));
     g.bytes = need;
     return OFDM_OK;
 }
 
 // Pinned host staging that only grows (contents not preserved).
-int ofdm::grow_host(ofdm_ctx* c, ofdm_ctx::Grow& g, size_t need)
+int ofdm::grow_host(ofdm_ctx* c, ofdm_ctx::GrowHost& g, size_t need)
 {
     if (need <= g.bytes) return OFDM_OK;
     HIP_TRY(hipSetDevice(c->device));
-    if (g.p) HIP_TRY(hipHostFree(g.p));
-    g.p = nullptr;
     g.bytes = 0;
-    HIP_TRY(hipHostMalloc(&g.p, need, hipHostMallocDefault));
+    HIP_TRY(g.p.reset());
+    HIP_TRY(hipHostMalloc(g.p.put(), need, hipHostMallocDefault));
     g.bytes = need;
     return OFDM_OK;
 }
@@ -232,438 +130,6 @@ extern "C" {
 
 const char* ofdm_last_error(void) { return g_err.c_str(); }
 int ofdm_abi_version(void) { return OFDM_MI355X_ABI_VERSION; }
-
-int ofdm_params_default(ofdm_params* o)
-{
-    if (!o) return fail(OFDM_ERR_INVALID, "null params");
-    *o = ofdm_params{};
-    o->fft_size = 512;
-    o->num_data_subc = 256;
-    o->num_pilot_subc = 8;
-    o->cp_size = 128;
-    o->num_symb = 8;
-    o->num_pr_symb = 1;
-    o->pr_sin_len = 128;
-    o->pr_seed = 42;
-    o->pr_level = 500;
-    o->t2sin_size = 256;
-    o->t2_sin_f1 = 17;
-    o->t2_sin_f2 = 51;
-    o->t2_sin_level = 800;
-    o->smooth = 5;
-    o->mod_type = 4;
-    o->pilot_ampl = 2500;
-    o->mult = 200;
-    o->rx_buf_size = 40;
-    o->iterations = 10000;
-    return OFDM_OK;
-}
-
-int ofdm_params_from_config(const char* path, ofdm_params* o)
-{
-    if (!o) return fail(OFDM_ERR_INVALID, "null params");
-    std::unordered_map<std::string, long> c;
-    int rc = parse_file(path, c);
-    if (rc) return rc;
-    // ConfigMap::operator[] semantics: missing keys read as 0
-    o->fft_size = c["fft_size"];
-    o->num_data_subc = c["num_data_subc"];
-    o->num_pilot_subc = c["num_pilot_subc"];
-    o->cp_size = c["cp_size"];
-    o->num_symb = c["num_symb"];
-    o->num_pr_symb = c["num_pr_symb"];
-    o->pr_sin_len = c["pr_sin_len"];
-    o->pr_seed = c["pr_seed"];
-    o->pr_level = c["pr_level"];
-    o->t2sin_size = c["T2sin_size"];
-    o->t2_sin_f1 = c["T2_sin_f1"];
-    o->t2_sin_f2 = c["T2_sin_f2"];
-    o->t2_sin_level = c["T2_sin_level"];
-    o->smooth = c["smooth"];
-    o->mod_type = c["modType"];
-    o->pilot_ampl = c["pilot_ampl"];
-    o->mult = c["mult"];
-    o->rx_buf_size = c["rx_buf_size"];
-    o->iterations = c["iterations"];
-    return OFDM_OK;
-}
-
-int ofdm_config_lookup(const char* path, const char* key, long* value)
-{
-    if (!key || !value) return fail(OFDM_ERR_INVALID, "null key/value");
-    std::unordered_map<std::string, long> c;
-    int rc = parse_file(path, c);
-    if (rc) return rc;
-    *value = c[key];
-    return OFDM_OK;
-}
-
-static int validate(const ofdm_params* p)
-{
-    const long N = p->fft_size, D = p->num_data_subc, P = p->num_pilot_subc, k = p->mod_type;
-    if (ilog2_exact(N) < 6 || ilog2_exact(N) > 12)
-        return fail(OFDM_ERR_UNSUPPORTED, "fft_size=%ld: the HIP FFT covers powers of two 64..4096", N);
-    if (P < 1 || D < P || D % P)
-        return fail(OFDM_ERR_UNSUPPORTED, "num_data_subc=%ld must be a positive multiple of num_pilot_subc=%ld", D,
-                    P);
-    if (P > 256) return fail(OFDM_ERR_UNSUPPORTED, "num_pilot_subc > 256");
-    if (!(k == 1 || k == 2 || k == 4 || k == 6 || k == 8))
-        return fail(OFDM_ERR_INVALID, "modType=%ld is not one of 1,2,4,6,8 (OFDM/modulation.hpp:11-17)", k);
-    if (p->cp_size < 0 || p->cp_size > N) return fail(OFDM_ERR_INVALID, "cp_size out of range");
-    if (p->num_symb < 1 || p->num_pr_symb < 1) return fail(OFDM_ERR_INVALID, "num_symb/num_pr_symb must be >= 1");
-    if ((D * p->num_symb * k) % 8 || (D * k) % 8)
-        return fail(OFDM_ERR_UNSUPPORTED, "num_data_subc*modType must be a multiple of 8 bits");
-    if ((D * p->num_pr_symb) % 8) return fail(OFDM_ERR_UNSUPPORTED, "preamble bits must fill bytes");
-    // layout must stay inside [1, N) without collisions: FFT_FORM ctor Frame.cpp:31-44
-    {
-        std::vector<char> used(N, 0);
-        const long step = D / P + 1, seg = D / P, half = P / 2;
-        long j = 0;
-        auto take = [&](long b) {
-            if (b < 1 || b >= N || used[b]) return false;
-            used[b] = 1;
-            return true;
-        };
-        for (long pos = 1 + seg; j < half; ++j, pos += step) {
-            if (!take(pos)) return fail(OFDM_ERR_INVALID, "pilot comb does not fit fft_size");
-            for (long t = 0; t < seg; ++t)
-                if (!take(pos - seg + t)) return fail(OFDM_ERR_INVALID, "data segments do not fit fft_size");
-        }
-        for (long pos = N - step * half; j < P; ++j, pos += step) {
-            if (!take(pos)) return fail(OFDM_ERR_INVALID, "pilot comb does not fit fft_size");
-            for (long t = 0; t < seg; ++t)
-                if (!take(pos + 1 + t)) return fail(OFDM_ERR_INVALID, "data segments do not fit fft_size");
-        }
-    }
-    if (p->t2sin_size < 0 || (p->t2sin_size && (p->t2_sin_f1 < 0 || p->t2_sin_f1 >= p->t2sin_size ||
-                                                p->t2_sin_f2 < 0 || p->t2_sin_f2 >= p->t2sin_size)))
-        return fail(OFDM_ERR_INVALID, "T2 tones outside T2sin_size");
-    if (p->pr_sin_len < 0 || p->pr_sin_len > (N + p->cp_size) * p->num_pr_symb)
-        return fail(OFDM_ERR_INVALID, "pr_sin_len exceeds the preamble");
-    return OFDM_OK;
-}
-
-int ofdm_destroy(ofdm_ctx* c)
-{
-    if (!c) return OFDM_OK;
-    (void)hipSetDevice(c->device);
-    void* ptrs[] = {c->d_tw, c->d_data_bin, c->d_data_slot, c->d_pilot_bin, c->d_bin_map, c->d_rx_pack,
-                    c->d_pilot_swz, c->d_tx_code, c->d_tx_dead, c->d_const,
-                    c->d_const_bpsk, c->d_header, c->d_preamble, c->d_templ, c->d_tspec, c->d_tspec32, c->d_twm, c->d_modpre,
-                    c->d_t2mask,
-                    c->d_t2tw, c->d_first, c->d_scratch, c->d_cfo_scratch, c->d_pre_hv, c->d_pre_done};
-    for (void* q : ptrs)
-        if (q) (void)hipFree(q);
-    for (auto* g : {&c->s_walk, &c->s_batch, &c->s_chan, &c->s_pbs, &c->s_pub, &c->s_chain})
-        if (g->p) (void)hipFree(g->p);
-    for (auto* g : {&c->h_walk, &c->h_frames, &c->h_status})
-        if (g->p) (void)hipHostFree(g->p);
-    if (c->d_queue) (void)hipFree(c->d_queue);
-    if (c->d_rxq) (void)hipFree(c->d_rxq);
-    if (c->ev_call) (void)hipEventDestroy(c->ev_call);
-    if (c->ev_walk) (void)hipEventDestroy(c->ev_walk);
-    if (c->ev_wdone) (void)hipEventDestroy(c->ev_wdone);
-    if (c->side) (void)hipStreamDestroy(c->side);
-    for (hipEvent_t ev : c->ev_phase)
-        if (ev) (void)hipEventDestroy(ev);
-    for (auto& pl : c->cfo_plans) {
-        if (pl.tw_sub) (void)hipFree(pl.tw_sub);
-        if (pl.tw_full) (void)hipFree(pl.tw_full);
-        if (pl.borders) (void)hipFree(pl.borders);
-    }
-    delete c;
-    return OFDM_OK;
-}
-
-// Modulation::Modulation table (modulation.cpp:4-36).
-static std::vector<double2> constellation(int k)
-{
-    std::vector<double2> t(1u << k);
-    if (k == 1) {
-        const double step = M_PI * 2 / (double)2;
-        for (int i = 0; i < 2; ++i) {
-            const cd z = std::exp(cd(0.0, 1.0) * (step * cd(i) + M_PI_4 * 5));
-            t[i] = make_double2(z.real(), z.imag());
-        }
-    } else {
-        const unsigned num = 1u << (k / 2);
-        for (unsigned i = 0; i < t.size(); ++i) {
-            const uint8_t in = (uint8_t)i;
-            t[i] = make_double2(2.0 / (num - 1) * double(in % num) - 1.0, 2.0 / (num - 1) * double(in >> (k / 2)) - 1.0);
-        }
-    }
-    return t;
-}
-
-int ofdm_create(const ofdm_params* params, int device, ofdm_ctx** out)
-{
-    if (!params || !out) return fail(OFDM_ERR_INVALID, "null argument");
-    *out = nullptr;
-    int rc = validate(params);
-    if (rc) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail(OFDM_ERR_HIP, "no HIP device available (the modem core has no CPU path)");
-    if (device < 0 || device >= ndev) return fail(OFDM_ERR_INVALID, "device %d out of range", device);
-    HIP_TRY(hipSetDevice(device));
-
-    ofdm_ctx* c = new ofdm_ctx;
-    c->p = *params;
-    c->device = device;
-    c->N = (int)params->fft_size;
-    c->logn = ilog2_exact(c->N);
-    c->D = (int)params->num_data_subc;
-    c->P = (int)params->num_pilot_subc;
-    c->cp = (int)params->cp_size;
-    c->S = (int)params->num_symb;
-    c->k = (int)params->mod_type;
-    c->L = c->N + c->cp;
-    c->seg = c->D / c->P;
-    c->npr = (int)params->num_pr_symb;
-    c->t2 = (int)params->t2sin_size;
-
-    ofdm_geometry& g = c->geo;
-    g.symbol_len = c->L;
-    g.message_len = (long)c->L * c->S;
-    g.preamble_len = (long)c->L * c->npr;
-    g.frame_len = c->t2 + g.preamble_len + g.message_len;
-    g.ring_len = g.frame_len * (params->rx_buf_size + 1);
-    g.data_per_frame = (long)c->D * c->S;
-    g.bytes_per_frame = (long)c->D * c->S * c->k / 8;
-    g.segment_size = c->seg;
-
-    // FFT_FORM layout (Frame.cpp:31-44)
-    std::vector<int> pilot(c->P), segst(c->P), data_bin(c->D), data_slot(c->D), bin_map(c->N, -1);
-    {
-        const int step = c->seg + 1, half = c->P / 2;
-        int j = 0;
-        for (int pos = 1 + c->seg; j < half; ++j, pos += step) {
-            pilot[j] = pos;
-            segst[j] = pos - c->seg;
-        }
-        for (int pos = c->N - step * half; j < c->P; ++j, pos += step) {
-            pilot[j] = pos;
-            segst[j] = pos + 1;
-        }
-        for (int jj = 0; jj < c->P; ++jj) {
-            g.pilot_bin[jj] = pilot[jj];
-            g.segment_bin[jj] = segst[jj];
-            bin_map[pilot[jj]] = -2;
-            for (int t = 0; t < c->seg; ++t) {
-                const int d = jj * c->seg + t;
-                data_bin[d] = segst[jj] + t;
-                data_slot[d] = jj;
-                bin_map[segst[jj] + t] = d;
-            }
-        }
-    }
-    // rx per-thread tables, zero-padded to the rx kernel's fixed per-thread
-    // counts (RX_DPT data and one pilot per thread) so it loads them unguarded
-    std::vector<int> rx_pack(std::max(c->D, ofdm::RX_DPT * (c->N / 8)), 0),
-        pilot_swz(std::max(c->P, c->N / 8), 0);
-    for (int d = 0; d < c->D; ++d) rx_pack[d] = ofdm::lds_swz_host(data_bin[d]) | (data_slot[d] << 16);
-    for (int j = 0; j < c->P; ++j) pilot_swz[j] = ofdm::lds_swz_host(pilot[j]);
-    // tx per-bin codes (ofdm_internal.hpp tx_code): data index + 0xff mask, or
-    // the pilot / zero entry of the kernel's LDS point table
-    std::vector<int> tx_code(c->N);
-    for (int b = 0; b < c->N; ++b)
-        tx_code[b] = bin_map[b] >= 0 ? ofdm::tx_code_data(bin_map[b])
-                                     : ofdm::tx_code_fixed(bin_map[b] == -2 ? ofdm::TX_LDS_PILOT : ofdm::TX_LDS_ZERO);
-    c->tx_code = tx_code;
-    c->tx_dead = ofdm::tx_dead_masks(tx_code);
-    if (std::any_of(c->tx_dead.begin(), c->tx_dead.end(), [](unsigned m) { return m != 0; }) &&
-        (rc = upload(&c->d_tx_dead, c->tx_dead))) {
-        ofdm_destroy(c);
-        return rc;
-    }
-    if ((rc = upload(&c->d_rx_pack, rx_pack)) || (rc = upload(&c->d_pilot_swz, pilot_swz)) ||
-        (rc = upload(&c->d_tx_code, tx_code)) ||
-        (rc = upload(&c->d_tw, twiddles(c->N))) || (rc = upload(&c->d_data_bin, data_bin)) ||
-        (rc = upload(&c->d_data_slot, data_slot)) || (rc = upload(&c->d_pilot_bin, pilot)) ||
-        (rc = upload(&c->d_bin_map, bin_map)) || (rc = upload(&c->d_const, constellation(c->k))) ||
-        (rc = upload(&c->d_const_bpsk, constellation(1)))) {
-        ofdm_destroy(c);
-        return rc;
-    }
-
-    if (c->k == 2) {  // the rx emit's fast path takes QPSK only (16-QAM measured no gain)
-        double* d_tau = nullptr;
-        double h_tau[4] = {};
-        hipError_t e = hipMalloc((void**)&d_tau, sizeof(h_tau));
-        if (e == hipSuccess) e = ofdm::launch_decide_tau_scan(c->k, d_tau, nullptr);
-        if (e == hipSuccess) e = hipMemcpy(h_tau, d_tau, sizeof(h_tau), hipMemcpyDeviceToHost);
-        if (d_tau) (void)hipFree(d_tau);
-        if (e != hipSuccess) {
-            ofdm_destroy(c);
-            return hip_fail(e, "decision threshold scan");
-        }
-        for (int j = 0; j < 3; ++j) c->dec_tau[j] = h_tau[j];
-        c->dec_fast = h_tau[3] == 1.0;
-    }
-
-    // T2SIN_FORM::set (Frame.cpp:139-154): X[f1] = X[f2] = 0.5, unnormalised
-    // backward DFT of T2sin_size points = two complex tones of amplitude 0.5.
-    c->t2_symbol.assign(c->t2, cd(0, 0));
-    if (c->t2) {
-        std::vector<cd> spec(c->t2, cd(0, 0));
-        spec[params->t2_sin_f1] = cd(0.5, 0);
-        spec[params->t2_sin_f2] = cd(0.5, 0);
-        for (int n = 0; n < c->t2; ++n) {
-            cd acc(0, 0);
-            for (int kk = 0; kk < c->t2; ++kk) {
-                if (spec[kk] == cd(0, 0)) continue;
-                const double a = 2.0 * M_PI * (double)(((long)kk * n) % c->t2) / (double)c->t2;
-                acc += spec[kk] * cd(std::cos(a), std::sin(a));
-            }
-            c->t2_symbol[n] = acc;
-        }
-    }
-    // T2 detector mask (Frame.cpp:120-133)
-    c->t2_mask.assign(std::max(1, c->t2), 0.0);
-    if (c->t2) {
-        const int sm = (int)params->smooth, f1 = (int)params->t2_sin_f1, f2 = (int)params->t2_sin_f2;
-        for (int i = std::max(0, f1 - sm); i <= std::min(c->t2 - 1, f1 + sm); ++i) c->t2_mask[i] += 1.0;
-        for (int i = std::max(0, f2 - sm); i <= std::min(c->t2 - 1, f2 + sm); ++i) c->t2_mask[i] += 1.0;
-    }
-
-    // PREAMBLE_FORM (Frame.cpp:259-294): mt19937(pr_seed) bytes, BPSK OFDM
-    // symbol(s) made by the tx kernel itself, conj template normalised.
-    {
-        const long nb = (long)c->D * c->npr / 8;
-        c->preamble_bytes.resize(nb);
-        std::mt19937 rng(params->pr_seed);
-        std::uniform_int_distribution<int> dist(0, 255);
-        for (auto& b : c->preamble_bytes) b = (uint8_t)dist(rng);
-
-        const long plen = g.preamble_len;
-        uint8_t* d_b = nullptr;
-        double2* d_pre = nullptr;
-        HIP_TRY(hipMalloc((void**)&d_b, std::max<long>(1, nb)));
-        HIP_TRY(hipMalloc((void**)&d_pre, plen * sizeof(double2)));
-        HIP_TRY(hipMemcpy(d_b, c->preamble_bytes.data(), nb, hipMemcpyHostToDevice));
-        ofdm::TxArgs a{};
-        a.tab = c->tables(true);
-        a.bytes = d_b;
-        a.iq = d_pre;
-        a.nframes = 1;
-        a.frame_stride = plen;
-        a.S = c->npr;
-        a.D = c->D;
-        a.P = c->P;
-        a.cp = c->cp;
-        a.k = 1;
-        a.bytes_per_frame = nb;
-        a.pilot_ampl = (double)params->pilot_ampl / 1000;
-        a.inv_sqrt_n = 1.0 / std::sqrt((double)c->N);
-        a.mult = (double)params->mult;
-        hipError_t e = ofdm::launch_tx(c->logn, a, nullptr);
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        std::vector<double2> pre(plen);
-        if (e == hipSuccess) e = hipMemcpy(pre.data(), d_pre, plen * sizeof(double2), hipMemcpyDeviceToHost);
-        (void)hipFree(d_b);
-        (void)hipFree(d_pre);
-        if (e != hipSuccess) {
-            ofdm_destroy(c);
-            return hip_fail(e, "preamble synthesis");
-        }
-        c->ofdm_preamble.resize(plen);
-        for (long i = 0; i < plen; ++i) c->ofdm_preamble[i] = cd(pre[i].x, pre[i].y);
-        // mod_preamble = Mod.mod(preamble) (BPSK points, bit_stream_converter(1,8))
-        const auto bp = constellation(1);
-        c->mod_preamble.resize((long)c->D * c->npr);
-        for (long i = 0; i < (long)c->mod_preamble.size(); ++i) {
-            const int bit = (c->preamble_bytes[i >> 3] >> (7 - (i & 7))) & 1;
-            c->mod_preamble[i] = cd(bp[bit].x, bp[bit].y);
-        }
-        const int Lt = (int)params->pr_sin_len;
-        c->templ.resize(Lt);
-        double norm = 0.0;
-        for (int i = 0; i < Lt; ++i) {
-            c->templ[i] = std::conj(c->ofdm_preamble[i]);
-            norm += std::abs(c->templ[i] * c->templ[i]);
-        }
-        norm = std::sqrt(norm);
-        for (int i = 0; i < Lt; ++i) c->templ[i] /= cd(norm);
-    }
-    {
-        std::vector<double2> hdr(c->t2 + g.preamble_len), pre(g.preamble_len), tpl(c->templ.size()),
-            mp(c->mod_preamble.size());
-        for (int i = 0; i < c->t2; ++i) hdr[i] = make_double2(c->t2_symbol[i].real(), c->t2_symbol[i].imag());
-        for (long i = 0; i < g.preamble_len; ++i) {
-            pre[i] = make_double2(c->ofdm_preamble[i].real(), c->ofdm_preamble[i].imag());
-            hdr[c->t2 + i] = pre[i];
-        }
-        for (size_t i = 0; i < tpl.size(); ++i) tpl[i] = make_double2(c->templ[i].real(), c->templ[i].imag());
-        // stream walker FFT search (ofdm_sync.hip walk_preamble_fft): template
-        // spectrum tspec_k = sum_j c_j e^{+2 pi i k j / M}, long double
-        std::vector<double2> tsp, twm;
-        if (params->pr_sin_len <= ofdm::WALK_FFT_M - 63) {  // windows of >= 64 lags
-            const int M = ofdm::WALK_FFT_M;
-            tsp.resize(M);
-            for (int k = 0; k < M; ++k) {
-                long double re = 0, im = 0;
-                for (size_t j = 0; j < c->templ.size(); ++j) {
-                    const long double a = 2.0L * 3.14159265358979323846264338327950288L * (long double)((k * (long)j) % M) / M;
-                    const long double cr = c->templ[j].real(), ci = c->templ[j].imag();
-                    const long double co = cosl(a), si = sinl(a);
-                    re += cr * co - ci * si;
-                    im += cr * si + ci * co;
-                }
-                tsp[k] = make_double2((double)re, (double)im);
-                c->tspec_max = std::max(c->tspec_max, std::hypot(tsp[k].x, tsp[k].y));
-            }
-            twm = twiddles(M);
-        }
-        for (size_t i = 0; i < mp.size(); ++i) mp[i] = make_double2(c->mod_preamble[i].real(), c->mod_preamble[i].imag());
-        std::vector<float2> tsp32(tsp.size());
-        for (size_t k = 0; k < tsp.size(); ++k) tsp32[k] = make_float2((float)tsp[k].x, (float)tsp[k].y);
-        if ((!tsp.empty() && ((rc = upload(&c->d_tspec, tsp)) || (rc = upload(&c->d_tspec32, tsp32)) ||
-                              (rc = upload(&c->d_twm, twm)))) ||
-            (rc = upload(&c->d_header, hdr)) || (rc = upload(&c->d_preamble, pre)) || (rc = upload(&c->d_templ, tpl)) ||
-            (rc = upload(&c->d_modpre, mp)) || (rc = upload(&c->d_t2mask, c->t2_mask))) {
-            ofdm_destroy(c);
-            return rc;
-        }
-    }
-    // T2 detector tables
-    // T2 detector scratch {min block = INT_MAX, done count = 0} (left so by
-    // every t2_scan launch), word 2: preamble_corr's start index
-    if ((rc = upload(&c->d_first, std::vector<int>{INT_MAX, 0, 0, 0}))) {
-        ofdm_destroy(c);
-        return rc;
-    }
-    // find_preamble's split scratch for up to PRE_SCRATCH_STARTS start indices
-    // (counters zero between launches); more starts per call take the
-    // one-workgroup form, so the entry point never allocates
-    {
-        const size_t cyc = 2 * (size_t)c->p.t2sin_size + (size_t)c->p.pr_sin_len;
-        if ((rc = upload(&c->d_pre_hv, std::vector<double>(ofdm_ctx::PRE_SCRATCH_STARTS * cyc, 0.0))) ||
-            (rc = upload(&c->d_pre_done, std::vector<unsigned>(ofdm_ctx::PRE_SCRATCH_STARTS, 0u)))) {
-            ofdm_destroy(c);
-            return rc;
-        }
-    }
-    if (c->t2 >= 64 && c->t2 <= 4096 && ilog2_exact(c->t2) > 0) {
-        c->t2_logn = ilog2_exact(c->t2);
-        if ((rc = upload(&c->d_t2tw, twiddles(c->t2)))) {
-            ofdm_destroy(c);
-            return rc;
-        }
-    }
-    // rx dynamic-frame counters: zero now, and left zero by every rx launch
-    const size_t qbytes = ofdm_ctx::RX_QUEUE_SLOTS * 16 * sizeof(int);
-    hipError_t qe = hipMalloc((void**)&c->d_rxq, qbytes);
-    if (qe == hipSuccess) qe = hipMemset(c->d_rxq, 0, qbytes);
-    if (qe == hipSuccess) qe = hipDeviceSynchronize();
-    if (qe != hipSuccess) {
-        ofdm_destroy(c);
-        return hip_fail(qe, "rx frame counters");
-    }
-    ofdm_walk_tuning_default(&c->walk);
-    c->ring = std::max(0L, c->p.rx_buf_size) * c->geo.frame_len;  // rx.cpp:53 / sdr.hpp:141
-    *out = c;
-    return OFDM_OK;
-}
 
 // The rx frame-queue slot of `st` (nullptr: no slot free, static frame order).
 static int* rx_queue(ofdm_ctx* c, hipStream_t st)
@@ -955,16 +421,10 @@ static int rx_demod_impl(ofdm_ctx* c, const double* iq, const int16_t* iq16, siz
             a.ystage = a.constell;
         } else {
             const size_t need = nframes * (size_t)c->S * c->D * sizeof(double2);
-            if (need > c->scratch_bytes) {
-                if (capturing((hipStream_t)stream)) return capture_refused("growing the staged rx scratch");
-                HIP_TRY(hipSetDevice(c->device));
-                if (c->d_scratch) HIP_TRY(hipFree(c->d_scratch));
-                c->d_scratch = nullptr;
-                c->scratch_bytes = 0;
-                HIP_TRY(hipMalloc((void**)&c->d_scratch, need));
-                c->scratch_bytes = need;
-            }
-            a.ystage = c->d_scratch;
+            if (need > c->d_scratch.bytes && capturing((hipStream_t)stream))
+                return capture_refused("growing the staged rx scratch");
+            if (int rc = grow(c, c->d_scratch, need)) return rc;
+            a.ystage = static_cast<double2*>(c->d_scratch.p.get());
         }
     }
     hipError_t e = soft ? ofdm::launch_rx_soft(c->logn, a, *soft, (hipStream_t)stream)
@@ -1598,7 +1058,7 @@ int ofdm_phase_sync(ofdm_ctx* c, double* x, size_t nframes, size_t stride, size_
 {
     if (!c || !x) return fail(OFDM_ERR_INVALID, "null argument");
     if (!pr) {
-        pr = reinterpret_cast<const double*>(c->d_preamble);
+        pr = reinterpret_cast<const double*>(c->d_preamble.get());
         pr_len = (size_t)c->geo.preamble_len;
     }
     if (pr_len > nsamples && nframes > 1 && stride < pr_len) return fail(OFDM_ERR_INVALID, "pr_len exceeds the form");
@@ -1715,17 +1175,11 @@ int ofdm_sync_frames(ofdm_ctx* c, double* frames, size_t nframes, size_t stride,
     if (stages & OFDM_SYNC_CFO) {
         double* dst = cfo_out;
         if (!dst) {
-            if (c->cfo_scratch_n < nframes) {
-                if (capturing((hipStream_t)stream))
-                    return capture_refused("growing the CFO scratch (cfo_out = NULL)");
-                HIP_TRY(hipSetDevice(c->device));
-                if (c->d_cfo_scratch) HIP_TRY(hipFree(c->d_cfo_scratch));
-                c->d_cfo_scratch = nullptr;
-                c->cfo_scratch_n = 0;
-                HIP_TRY(hipMalloc((void**)&c->d_cfo_scratch, nframes * sizeof(double)));
-                c->cfo_scratch_n = nframes;
-            }
-            dst = c->d_cfo_scratch;
+            const size_t need = nframes * sizeof(double);
+            if (need > c->d_cfo_scratch.bytes && capturing((hipStream_t)stream))
+                return capture_refused("growing the CFO scratch (cfo_out = NULL)");
+            if ((rc = grow(c, c->d_cfo_scratch, need))) return rc;
+            dst = static_cast<double*>(c->d_cfo_scratch.p.get());
         }
         if ((rc = ofdm_cfo_estimate(c, frames, nframes, stride, c->npr, dst, stream))) return rc;
         cfo = dst;
@@ -1828,8 +1282,8 @@ int ofdm_set_stream_timing(ofdm_ctx* c, int on)
 {
     if (!c || (on != 0 && on != 1)) return fail(OFDM_ERR_INVALID, "need a ctx and on = 0 or 1");
     HIP_TRY(hipSetDevice(c->device));
-    for (hipEvent_t& ev : c->ev_phase)
-        if (on && !ev) HIP_TRY(hipEventCreate(&ev));
+    for (ofdm::Event& ev : c->ev_phase)
+        if (on && !ev) HIP_TRY(hipEventCreate(ev.put()));
     c->phase_timing = on != 0;
     c->phase_valid = false;
     return OFDM_OK;

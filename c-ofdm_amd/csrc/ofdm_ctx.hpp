@@ -1,6 +1,9 @@
 // ofdm_ctx.hpp — the modem context behind the C-ABI's opaque ofdm_ctx, and the
-// helpers that both host files use: ofdm_capi.cpp (which defines them) and
-// ofdm_stream_call.cpp. Host code only: no .hip file includes this header.
+// helpers that the three host files share: ofdm_create.cpp (the context's life
+// cycle and its tables), ofdm_capi.cpp (the entry points) and
+// ofdm_stream_call.cpp (the stream receiver). Every HIP resource of the context
+// is held by an owner (ofdm_owned.hpp), so deleting the context releases them
+// all. Host code only: no .hip file includes this header.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,10 +14,13 @@
 
 #include "../../include/ofdm_mi355x.h"
 #include "ofdm_internal.hpp"
+#include "ofdm_owned.hpp"
 
 using cd = std::complex<double>;
 
 struct ofdm_ctx {
+    template <class T>
+    using DevBuf = ofdm::DevBuf<T>;
     ofdm_params p{};
     int device = 0;
     int logn = 0;
@@ -25,101 +31,104 @@ struct ofdm_ctx {
     std::vector<uint8_t> preamble_bytes;
     std::vector<double> t2_mask;
     // device tables
-    double2* d_tw = nullptr;
-    int* d_data_bin = nullptr;
-    int* d_data_slot = nullptr;
-    int* d_pilot_bin = nullptr;
-    int* d_bin_map = nullptr;
-    int* d_rx_pack = nullptr;
-    int* d_pilot_swz = nullptr;
-    int* d_tx_code = nullptr;
+    DevBuf<double2> d_tw;
+    DevBuf<int> d_data_bin;
+    DevBuf<int> d_data_slot;
+    DevBuf<int> d_pilot_bin;
+    DevBuf<int> d_bin_map;
+    DevBuf<int> d_rx_pack;
+    DevBuf<int> d_pilot_swz;
+    DevBuf<int> d_tx_code;
     // tx dead-group masks (ofdm_internal.hpp tx_dead_masks); d_tx_dead stays
     // null when no wave has a dead group. tx_sparse: ofdm_tx_sparse's switch
     std::vector<int> tx_code;
     std::vector<unsigned> tx_dead;
-    unsigned* d_tx_dead = nullptr;
+    DevBuf<unsigned> d_tx_dead;
 #ifndef OFDM_TX_SPARSE_DEFAULT  // 0: an A/B build (tools/build_variant.sh) that maps every group
 #define OFDM_TX_SPARSE_DEFAULT 1
 #endif
     bool tx_sparse = OFDM_TX_SPARSE_DEFAULT != 0;
-    double2* d_const = nullptr;
-    double2* d_const_bpsk = nullptr;
+    DevBuf<double2> d_const;
+    DevBuf<double2> d_const_bpsk;
     // decide_select's thresholds (the rx emit's fast path, k = 2), found on
     // the device at creation; dec_fast = false: the scan's checks failed or
     // k is not 2, and rx keeps the decision arithmetic
     double dec_tau[3] = {};
     bool dec_fast = false;
-    double2* d_header = nullptr;   // T2 + preamble
-    double2* d_preamble = nullptr; // ofdm_preamble (preamble_len)
-    double2* d_templ = nullptr;    // pr_sin_len
-    double2* d_tspec = nullptr;    // WALK_FFT_M template spectrum (stream walker FFT search)
-    float2* d_tspec32 = nullptr;   // the same rounded to FP32 (the search's FP32 tier)
-    double2* d_twm = nullptr;      // WALK_FFT_M twiddles
+    DevBuf<double2> d_header;      // T2 + preamble
+    DevBuf<double2> d_preamble;    // ofdm_preamble (preamble_len)
+    DevBuf<double2> d_templ;       // pr_sin_len
+    DevBuf<double2> d_tspec;       // WALK_FFT_M template spectrum (stream walker FFT search)
+    DevBuf<float2> d_tspec32;      // the same rounded to FP32 (the search's FP32 tier)
+    DevBuf<double2> d_twm;         // WALK_FFT_M twiddles
     double tspec_max = 0.0;
-    double2* d_modpre = nullptr;   // D*npr
-    double* d_t2mask = nullptr;    // t2 size
-    double2* d_t2tw = nullptr;     // t2-size twiddles (T2 detector)
-    int* d_first = nullptr;        // T2 detector min-block scratch
+    DevBuf<double2> d_modpre;      // D*npr
+    DevBuf<double> d_t2mask;       // t2 size
+    DevBuf<double2> d_t2tw;        // t2-size twiddles (T2 detector)
+    DevBuf<int> d_first;           // T2 detector min-block scratch
     int t2_logn = -1;              // T2sin_size = 2^t2_logn, else -1 (detector unsupported)
     struct CfoPlan {               // pilot_freq_sinh on a form of nsym symbols
         int nsym = 0, logm = -1, g = 0;
-        double2* tw_sub = nullptr;
-        double2* tw_full = nullptr;
-        int* borders = nullptr;
+        DevBuf<double2> tw_sub;
+        DevBuf<double2> tw_full;
+        DevBuf<int> borders;
     };
     std::vector<CfoPlan> cfo_plans;
-    double* d_cfo_scratch = nullptr;
-    size_t cfo_scratch_n = 0;
-    // staged-rx scratch (grown on demand, only for num_symb > 8 or D > N/2)
-    double2* d_scratch = nullptr;
-    size_t scratch_bytes = 0;
-    // ofdm_rx_stream scratch (grown on demand): walker records, frame batch,
-    // channel estimates, frame starts
-    struct Grow {
-        void* p = nullptr;
+    // scratch that only grows (ofdm::grow / ofdm::grow_host): an owner and its size
+    template <class Own>
+    struct Grown {
+        Own p;
         size_t bytes = 0;
     };
+    using Grow = Grown<DevBuf<void>>;
+    using GrowHost = Grown<ofdm::HostBlock>;
+    // ofdm_sync_frames' CFO estimates where the caller takes none, and the
+    // staged-rx scratch (only for num_symb > 8 or D > N/2)
+    Grow d_cfo_scratch, d_scratch;
+    // ofdm_rx_stream scratch (grown on demand): walker records, frame batch,
+    // channel estimates, frame starts
     Grow s_walk, s_batch, s_chan, s_pbs;
     // find_preamble's split form: magnitudes and per-start counters (zero
     // between launches) for up to PRE_SCRATCH_STARTS start indices per call
     static constexpr size_t PRE_SCRATCH_STARTS = 64;
-    double* d_pre_hv = nullptr;
-    unsigned* d_pre_done = nullptr;
+    DevBuf<double> d_pre_hv;
+    DevBuf<unsigned> d_pre_done;
     // pinned host staging for the walk records and the frame list (pageable
     // copies go through a driver bounce buffer and synchronise twice)
-    Grow h_walk, h_frames;
+    GrowHost h_walk, h_frames;
     hipStream_t h_frames_stream = nullptr;  // stream of the last copy out of h_frames
     bool h_frames_used = false;
-    int* d_queue = nullptr;        // walker chunk counter (zero between calls)
+    DevBuf<int> d_queue;           // walker chunk counter (zero between calls)
     // rx dynamic-frame counters {next, done}, zero between launches: one slot
     // per HIP stream that launched rx on this context (launches on one stream
     // run in order, so each slot is reset by the launch before the next uses
     // it); streams past RX_QUEUE_SLOTS run with a static frame order
     static constexpr int RX_QUEUE_SLOTS = 32;
-    int* d_rxq = nullptr;          // RX_QUEUE_SLOTS x 16 ints (one 64-B line each)
+    DevBuf<int> d_rxq;             // RX_QUEUE_SLOTS x 16 ints (one 64-B line each)
     hipStream_t rxq_stream[RX_QUEUE_SLOTS] = {};
     bool rxq_live[RX_QUEUE_SLOTS] = {};  // slot bound to rxq_stream[i] (false: freed by ofdm_stream_destroy)
     int rxq_used = 0;
     ofdm_walk_tuning walk{};       // stream walker settings (ofdm_set_walk_tuning)
     long ring = 0;                 // rx.cpp's SDR ring R (ofdm_set_stream_ring; 0: the continuous walk)
     bool queue_zero = false;       // the last stream call's compaction left the walker counter zero
-    hipEvent_t ev_call = nullptr;  // recorded on call_stream when a stream call comes on another stream
+    ofdm::Event ev_call;           // recorded on call_stream when a stream call comes on another stream
     hipStream_t call_stream = nullptr;  // the last stream call's HIP stream
     bool call_valid = false;       //   (call_stream set)
-    hipEvent_t ev_walk = nullptr;  // walk records landed in h_walk
-    hipEvent_t ev_wdone = nullptr;  // the walk kernel finished (caller's stream)
-    hipStream_t side = nullptr;     // copies the walk records out beside the decode
+    ofdm::Event ev_walk;           // walk records landed in h_walk
+    ofdm::Event ev_wdone;          // the walk kernel finished (caller's stream)
+    ofdm::Stream side;             // copies the walk records out beside the decode
     // look-back walk: per-chunk publication counts (zero between calls: the
     // resolve kernel clears them), the true walk's records for shard reports,
     // and the resolve kernel's status block (page-locked, written by the kernel)
-    Grow s_pub, s_chain, h_status;
+    Grow s_pub, s_chain;
+    GrowHost h_status;
     bool pub_zero = false;         // every s_pub word is zero
     // per-phase device times of the last look-back stream call
     // (ofdm_set_stream_timing): events before the walk, after the walk, after
     // the resolve and after the decode, on the call's stream
     bool phase_timing = false;
     bool phase_valid = false;
-    hipEvent_t ev_phase[4] = {};
+    ofdm::Event ev_phase[4];
 
     ofdm::DevTables tables(bool bpsk) const
     {
@@ -139,6 +148,10 @@ struct ofdm_ctx {
 
 namespace ofdm {
 
+// ---- defined in ofdm_create.cpp ----
+// pilot_freq_sinh plan for a form of nsym symbols (built on first use)
+int cfo_plan(ofdm_ctx* c, int nsym, ofdm_ctx::CfoPlan** out, hipStream_t st);
+
 // ---- defined in ofdm_capi.cpp ----
 // sets ofdm_last_error's text for this thread; returns `code`
 int fail(int code, const char* fmt, ...);
@@ -153,9 +166,7 @@ int hip_fail(hipError_t e, const char* what);
 bool aligned16(const void* p);
 // device scratch / pinned host staging that only grows (contents not preserved)
 int grow(ofdm_ctx* c, ofdm_ctx::Grow& g, size_t need);
-int grow_host(ofdm_ctx* c, ofdm_ctx::Grow& g, size_t need);
-// pilot_freq_sinh plan for a form of nsym symbols (built on first use)
-int cfo_plan(ofdm_ctx* c, int nsym, ofdm_ctx::CfoPlan** out, hipStream_t st);
+int grow_host(ofdm_ctx* c, ofdm_ctx::GrowHost& g, size_t need);
 // whether `st` is being captured into a hipGraph, and the refusal of a call
 // that a capture does not allow
 bool capturing(hipStream_t st);

@@ -261,7 +261,7 @@ int fill_walk_args(ofdm_ctx* c, const StreamCall& a, const WalkPlan& p, const Wa
     // drains it, slower walkers taking fewer chunks. The counter is zeroed by
     // the previous call's compaction (stream order), else by launch_walk.
     if (!c->d_queue) {
-        HIP_TRY(hipMalloc((void**)&c->d_queue, 64));
+        HIP_TRY(hipMalloc((void**)c->d_queue.put(), 64));
         c->queue_zero = false;
     }
     w.queue = c->d_queue;
@@ -280,7 +280,7 @@ int fill_walk_args(ofdm_ctx* c, const StreamCall& a, const WalkPlan& p, const Wa
 int order_after_previous_call(ofdm_ctx* c, hipStream_t st)
 {
     if (c->call_valid && c->call_stream != st) {
-        if (!c->ev_call) HIP_TRY(hipEventCreateWithFlags(&c->ev_call, hipEventDisableTiming));
+        if (!c->ev_call) HIP_TRY(hipEventCreateWithFlags(c->ev_call.put(), hipEventDisableTiming));
         if (hipEventRecord(c->ev_call, c->call_stream) == hipSuccess) {
             HIP_TRY(hipStreamWaitEvent(st, c->ev_call, 0));
         } else {
@@ -346,7 +346,7 @@ int launch_walk(ofdm_ctx* c, Walk& wk, hipStream_t st)
         if (!c->pub_zero) HIP_TRY(hipMemsetAsync(c->s_pub.p, 0, c->s_pub.bytes, st));
         c->pub_zero = false;  // until the resolve kernel clears it again
         w.lookback = 1;
-        w.pub = static_cast<int*>(c->s_pub.p);
+        w.pub = static_cast<int*>(c->s_pub.p.get());
         w.link = wk.dev.link;
     }
     // only the T2 size with a diagnostics walker writes a timeline; any other
@@ -415,7 +415,7 @@ int decode_fused(const Decode& d, const long* d_list, size_t nb_total, const lon
     const size_t nb0 = std::min(nb_total, bmax);
     int r2;
     if ((r2 = grow(c, c->s_chan, nb0 * d.per))) return r2;
-    double2* chan = static_cast<double2*>(c->s_chan.p);
+    double2* chan = static_cast<double2*>(c->s_chan.p.get());
     double2* corr = chan + nb0 * c->D;
     double* cfo_tmp = reinterpret_cast<double*>(corr + nb0 * c->S * CORR_PER_SYM);
     for (size_t f0 = 0; f0 < nb_total; f0 += nb0) {
@@ -511,8 +511,8 @@ int decode_gathered(const Decode& d, const long* d_list, size_t nout)
     const size_t nb0 = std::min(nout, bmax);
     int r2;
     if ((r2 = grow(c, c->s_batch, nb0 * fb)) || (r2 = grow(c, c->s_chan, nb0 * c->D * sizeof(double2)))) return r2;
-    double* batch = static_cast<double*>(c->s_batch.p);
-    double* chan = static_cast<double*>(c->s_chan.p);
+    double* batch = static_cast<double*>(c->s_batch.p.get());
+    double* chan = static_cast<double*>(c->s_chan.p.get());
     for (size_t f0 = 0; f0 < nout; f0 += nb0) {
         const size_t nb = std::min(nb0, nout - f0);
         GatherArgs ga{reinterpret_cast<const double2*>(a.iq), reinterpret_cast<const short2*>(a.iq16), (long)a.n,
@@ -586,8 +586,8 @@ int finish_lookback(ofdm_ctx* c, const StreamCall& a, const Walk& wk, const Deco
     if ((rc = grow(c, c->s_pbs, (ub + 1) * sizeof(long))) || (rc = grow_host(c, c->h_status, 64)) ||
         (want_chain && (rc = grow(c, c->s_chain, a.located_cap * sizeof(long)))))
         return rc;
-    long* d_pbs = static_cast<long*>(c->s_pbs.p);
-    volatile long* hs = static_cast<volatile long*>(c->h_status.p);
+    long* d_pbs = static_cast<long*>(c->s_pbs.p.get());
+    volatile long* hs = static_cast<volatile long*>(c->h_status.p.get());
     hs[1] = -1;  // overwritten by the resolve kernel
     ResolveArgs ra{};
     ra.rec = wk.dev.rec;
@@ -605,7 +605,7 @@ int finish_lookback(ofdm_ctx* c, const StreamCall& a, const Walk& wk, const Deco
     ra.list = d_pbs;
     ra.list2 = a.pb_out;
     ra.count = d_pbs + ub;
-    ra.chain = want_chain ? static_cast<long*>(c->s_chain.p) : nullptr;
+    ra.chain = want_chain ? static_cast<long*>(c->s_chain.p.get()) : nullptr;
     ra.chain_head = (long)chain_head;
     ra.chain_tail = (long)chain_tail;
     ra.status = const_cast<long*>(hs);
@@ -654,7 +654,7 @@ int finish_lookback(ofdm_ctx* c, const StreamCall& a, const Walk& wk, const Deco
 int launch_compaction(ofdm_ctx* c, const StreamCall& a, const Walk& wk, size_t ub, hipStream_t st)
 {
     if (int rc = grow(c, c->s_pbs, (ub + 1) * sizeof(long))) return rc;
-    long* d_pbs = static_cast<long*>(c->s_pbs.p);
+    long* d_pbs = static_cast<long*>(c->s_pbs.p.get());
     CompactArgs ka{};
     ka.rec = wk.dev.rec;
     ka.ncore = wk.dev.ncore;
@@ -734,7 +734,7 @@ int decode_stitched(ofdm_ctx* c, const StreamCall& a, const Decode& dec, const s
     if ((rc = grow(c, c->s_pbs, (std::max(nout, ub) + 1) * sizeof(long))) ||
         (rc = grow_host(c, c->h_frames, nout * sizeof(long))))
         return rc;
-    long* d_pbs = static_cast<long*>(c->s_pbs.p);
+    long* d_pbs = static_cast<long*>(c->s_pbs.p.get());
     // the previous call's copy out of the pinned stage must have finished: on
     // the same stream the walk-record sync before the stitch saw to it
     if (c->h_frames_used && c->h_frames_stream != st) HIP_TRY(hipStreamSynchronize(c->h_frames_stream));
@@ -759,9 +759,9 @@ int finish_halo(ofdm_ctx* c, const StreamCall& a, const Walk& wk, const Decode& 
     // records, exit states and counts in one copy of the walk buffer's layout
     if ((rc = grow_host(c, c->h_walk, wk.buf.host_bytes()))) return rc;
     const WalkView host = wk.buf.view(c->h_walk.p);
-    if (!c->ev_walk) HIP_TRY(hipEventCreateWithFlags(&c->ev_walk, hipEventDisableTiming));
-    if (!c->ev_wdone) HIP_TRY(hipEventCreateWithFlags(&c->ev_wdone, hipEventDisableTiming));
-    if (!c->side) HIP_TRY(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
+    if (!c->ev_walk) HIP_TRY(hipEventCreateWithFlags(c->ev_walk.put(), hipEventDisableTiming));
+    if (!c->ev_wdone) HIP_TRY(hipEventCreateWithFlags(c->ev_wdone.put(), hipEventDisableTiming));
+    if (!c->side) HIP_TRY(hipStreamCreateWithFlags(c->side.put(), hipStreamNonBlocking));
     // Speculative decode: every chunk's in-core records, compacted on the
     // device behind the walk, are decoded while the host stitches the walks.
     // That list is the stitched walk unless a chunk needs a re-walk (or the
@@ -778,7 +778,7 @@ int finish_halo(ofdm_ctx* c, const StreamCall& a, const Walk& wk, const Decode& 
     HIP_TRY(hipMemcpyAsync(host.rec, wk.dev.rec, wk.buf.host_bytes(), hipMemcpyDeviceToHost, c->side));
     HIP_TRY(hipEventRecord(c->ev_walk, c->side));
     if (spec) {
-        const long* d_pbs = static_cast<const long*>(c->s_pbs.p);
+        const long* d_pbs = static_cast<const long*>(c->s_pbs.p.get());
         if ((rc = decode_fused(dec, d_pbs, ub, d_pbs + ub))) return rc;
         // the queue counter was zeroed by the compaction (stream order)
         c->queue_zero = true;

@@ -105,7 +105,7 @@ def layout_ok(N, D, P):
 
 
 def valid(c):
-    """validate() (csrc/ofdm_capi.cpp) and rx_dispatch's P <= T on one config."""
+    """validate() (csrc/ofdm_create.cpp) and rx_dispatch's P <= T on one config."""
     N, D, P, k = c["fft_size"], c["num_data_subc"], c["num_pilot_subc"], c["mod_type"]
     S, cp = c["num_symb"], c["cp_size"]
     return (N in (64, 128, 256, 512, 1024, 2048, 4096) and P >= 2 and P % 2 == 0 and D % P == 0 and D % 8 == 0

@@ -41,7 +41,7 @@ LD = dt.LD
 
 def masks(n):
     sm, f1, f2 = D["smooth"], D["t2_sin_f1"], D["t2_sin_f2"]
-    clip = lambda f: (max(0, f - sm), min(n - 1, f + sm))  # noqa: E731  (as ofdm_capi.cpp builds the ranges)
+    clip = lambda f: (max(0, f - sm), min(n - 1, f + sm))  # noqa: E731  (as ofdm_tables.hpp builds the ranges)
     return {"default": clip(f1) + clip(f2), "overlap": clip(f1) + clip(f1 + sm + 1), "clipped": clip(2) + clip(n - 3)}
 
 
@@ -164,7 +164,7 @@ M = 512
 
 
 def template_spectrum(templ):
-    """tspec_k = sum_j c_j e^{+2 pi i k j / M} in longdouble (as ofdm_capi.cpp
+    """tspec_k = sum_j c_j e^{+2 pi i k j / M} in longdouble (as ofdm_tables.hpp
     builds it), so that IDFT(DFT(x) . tspec)_i = sum_j x[i + j] c_j."""
     c = np.zeros(M, dt.CLD)
     c[: len(templ)] = templ

@@ -5,7 +5,7 @@ reaches; the fixtures themselves are checked on the CPU in
 tests/test_tx_cases.py). No torch, no GPU: numpy and the oracle.
 
 - CASES: the geometry table, overrides of O.DEFAULT. tx takes what
-  validate() (csrc/ofdm_capi.cpp) takes: unlike rx it has no D <= N/2 and no
+  validate() (csrc/ofdm_create.cpp) takes: unlike rx it has no D <= N/2 and no
   P <= T limit.
 - expected_instance: tx_launch_modes (csrc/ofdm_kernels.hip) restated. The C
   ABI reaches 35 instances of tx_kernel<LOGN, POINTS, NOISE, I16>: per LOGN
@@ -94,7 +94,7 @@ FRAME_CASES = ("N64-D32-P4-cp5-k8-S200", "N512-D256-P8-cp128-k4-S16", "N4096-D20
 
 # ------------------------------------------------------------------ the library's rules, restated
 def valid(c):
-    """validate() (csrc/ofdm_capi.cpp) on one config: what ofdm_create, and so tx, takes."""
+    """validate() (csrc/ofdm_create.cpp) on one config: what ofdm_create, and so tx, takes."""
     N, D, P, k = c["fft_size"], c["num_data_subc"], c["num_pilot_subc"], c["mod_type"]
     S, cp, npr, t2 = c["num_symb"], c["cp_size"], c["num_pr_symb"], c["t2sin_size"]
     return (N in (64, 128, 256, 512, 1024, 2048, 4096) and P >= 1 and D >= P and D % P == 0 and P <= 256
